@@ -10,6 +10,7 @@ check + fused AdamW + loss-scale update, all on the hand-written HIP path.  Inpu
 HBM before the timed region.
 
     python bench.py --gpus N --steps K --warmup W [--workload recon|moco|joint|spark] [--dtype f16|bf16|f32]
+                    [--dump-outputs DIR] [--full]
 
 N > 1: one rank per GPU over RCCL.  Either launched by torch.distributed.run (RANK / LOCAL_RANK / WORLD_SIZE in the
 environment) or directly -- then this process only spawns its N ranks (it never touches the GPU itself) and exits with
@@ -20,11 +21,19 @@ Other workloads (same bs 32 / GPU, 512x512; BASELINE configs 3-5):
     joint  CM_UNet contrastive + masked reconstruction (projector in = 262,144), AdamW, EMA of the target networks
     spark  SparK sparse masked-conv encoder (mask 0.75: 256 of 1,024 patches active) + UNet decoder, LAMB
 
-Rank 0 prints ONE JSON line: metric images/sec (whole job), roofline of the dominant kernel (algorithmic FLOPs of its
-launches / their HIP-event time, measured inside the timed region) and the CPU baseline (the oracle's torch-CPU
-restatement of the same step on a bounded sample, N=1 only).  By default the HIP events bracket the GEMM-shaped entry
+Rank 0 prints ONE JSON line: metric images/sec (whole job) and ms_per_step of the K timed steps.  A plain run does only
+that: set-up, W warm-up steps, the K timed steps, the outputs (--dump-outputs) and the line.
+
+--dump-outputs DIR: after the timed steps, rank 0 writes what the last timed step handed back -- its loss and the model's
+state after it (parameters and buffers; a fixed seeded sample of the larger tensors) -- as DIR/<name>.npy, so that two
+builds can be compared output for output (the inputs and initial weights are seeded: the same arguments give the same inputs).
+
+--full adds the diagnostics, each measured after the timed steps: a second pass of K steps with HIP events around the
+launches gives the roofline of the dominant kernel (algorithmic FLOPs of its launches / their HIP-event time), the
+per-kernel tables and the whole-step rooflines; the sustained MFMA rate of the chip; and the CPU baseline (the oracle's
+torch-CPU restatement of the same step on a bounded sample, N=1 only).  The HIP events bracket the GEMM-shaped entry
 points only (~80 launches of a step: what the roofline needs); --all-kernel-events brackets every entry point and prints
-the full kernel_ms_per_step table at ~0.5 ms per step (1.2 % of it).
+the full kernel_ms_per_step table.
 """
 import argparse
 import json
@@ -236,6 +245,26 @@ def step_roofline(workload, H, dtype, img_s):
             "note": "SURVEY 8(d): algorithmic FLOPs / bytes per layer (x3 for a trained pass); peaks 2.5 PFLOP/s (16-bit) and 8 TB/s"}
 
 
+def dump_outputs(d, loss, model, budget_elems=12 << 20, per_tensor=1 << 16):
+    """--dump-outputs: the loss of the last timed step (float64) and every floating tensor of the model's state_dict() after it
+    (float32, one file each: DIR/loss.npy, DIR/state.<name>.npy).  A tensor above ``per_tensor`` elements (less when the model has
+    many tensors: ``budget_elems`` in all, 48 MiB) is written as a sample of its flattened values, at indices seeded by its name --
+    the same elements in every run."""
+    import zlib
+    import numpy as np
+    import torch
+    os.makedirs(d, exist_ok=True)
+    np.save(os.path.join(d, "loss.npy"), loss.detach().reshape(-1).double().cpu().numpy())
+    state = {k: v for k, v in model.state_dict().items() if torch.is_tensor(v) and v.is_floating_point()}
+    cap = max(1, min(per_tensor, budget_elems // max(1, len(state))))
+    for k, v in state.items():
+        v = v.detach()
+        if v.numel() > cap:
+            idx = np.sort(np.random.RandomState(zlib.crc32(k.encode())).randint(0, v.numel(), cap, dtype=np.int64))
+            v = v.reshape(-1)[torch.from_numpy(idx).to(v.device)]
+        np.save(os.path.join(d, f"state.{k}.npy"), v.float().cpu().numpy())
+
+
 # ---------------------------------------------------------------------------------------------------------------------
 # self-launch (python bench.py --gpus N without a launcher)
 # ---------------------------------------------------------------------------------------------------------------------
@@ -397,11 +426,16 @@ def main():
     ap.add_argument("--dtype", default="f16", choices=["bf16", "f16", "f32"],
                     help="activation / MFMA operand type (f16 = the reference's AMP arithmetic, cmunet_config.py:76-78)")
     ap.add_argument("--workload", default="recon", choices=["recon", "moco", "joint", "spark"])
-    ap.add_argument("--no-cpu-baseline", action="store_true")
-    ap.add_argument("--no-kernel-events", action="store_true", help="skip per-launch HIP events (pure throughput run)")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="write the last timed step's loss and the model state after it as DIR/<name>.npy (float32 / float64)")
+    ap.add_argument("--full", action="store_true",
+                    help="also measure the diagnostics after the timed steps: roofline and per-kernel tables (a profiled pass of "
+                         "--steps steps), sustained MFMA rate, CPU baseline")
+    ap.add_argument("--no-cpu-baseline", action="store_true", help="(--full) skip the CPU baseline")
+    ap.add_argument("--no-kernel-events", action="store_true", help="(--full) skip the profiled pass with per-launch HIP events")
     ap.add_argument("--all-kernel-events", action="store_true",
-                    help="HIP events around EVERY entry point (the full kernel_ms_per_step table: ~460 events per step cost ~0.5 ms of "
-                         "the 41 ms) instead of the GEMM-shaped entries only (the default: what the roofline needs, ~0.15 ms)")
+                    help="(--full) HIP events around EVERY entry point (the full kernel_ms_per_step table: ~460 events per step cost "
+                         "~0.5 ms of the 41 ms) instead of the GEMM-shaped entries only (the default: what the roofline needs, ~0.15 ms)")
     ap.add_argument("--gemm-events-only", action="store_true", help="(default behaviour; kept for scripts)")
     ap.add_argument("--graph", action="store_true", help="capture the step of each pre-staged batch in a hipGraph and replay it "
                     "(experiment: removes the host's ~230 launches per step; implies --no-kernel-events)")
@@ -410,6 +444,8 @@ def main():
                          "batch, learning-rate rule, queue divisibility), the ranks meet in a CPU (gloo) group, compare their plans and "
                          "rank 0 prints them as one JSON line -- no GPU is touched (tests/test_cpu_distributed.py runs --gpus 8 this way)")
     args = ap.parse_args()
+    if args.steps < 1 or args.warmup < 0:
+        ap.error("--steps must be at least 1 and --warmup at least 0")
 
     if args.gpus > 1 and "WORLD_SIZE" not in os.environ:
         sys.exit(spawn_ranks(args.gpus, sys.argv[1:]))
@@ -476,17 +512,12 @@ def main():
             gph, out_b = graphs[i % 2]
             gph.replay()
             return out_b
-    prof = None
-    if not args.no_kernel_events:
-        prof = _lib.EventProfiler(gemm_only=not args.all_kernel_events)
-        _lib.PROFILER = prof
     sync()
     t0 = time.perf_counter()
     for i in range(args.steps):
         loss = step(i)
     sync()
     elapsed = time.perf_counter() - t0
-    _lib.PROFILER = None
     rccl = None
     if use_dist:
         t = torch.tensor([elapsed], dtype=torch.float64, device=dev)
@@ -531,6 +562,21 @@ def main():
     }
     if rccl is not None:
         out["rccl"] = rccl
+    if rank == 0 and args.dump_outputs:
+        if hasattr(tr, "finish_pending"):
+            tr.finish_pending()            # (N > 1, joint: the sharded projector's all-gather may still be in flight)
+        dump_outputs(args.dump_outputs, loss, tr.model)
+    prof = None
+    if args.full and not args.no_kernel_events:
+        # the profiled pass: K more steps with HIP events around the launches (every rank steps: the collectives need all of them);
+        # after the dump above -- the trainers reuse their loss tensor
+        prof = _lib.EventProfiler(gemm_only=not args.all_kernel_events)
+        _lib.PROFILER = prof
+        sync()
+        for i in range(args.steps):
+            step(args.steps + i)
+        sync()
+        _lib.PROFILER = None
     if rank == 0 and prof is not None:
         summ = prof.summary()
         tot_ms = sum(v["ms"] for v in summ.values())
@@ -602,7 +648,7 @@ def main():
         out["step_mfma_tflops"] = round(flops_step / (elapsed / args.steps) / 1e12, 2)
         if H == W:
             out["step_roofline"] = step_roofline(args.workload, H, args.dtype, out["value"] / world)
-    if rank == 0 and world == 1 and not args.no_cpu_baseline:
+    if rank == 0 and world == 1 and args.full and not args.no_cpu_baseline:
         try:
             out["cpu_baseline"] = cpu_baseline(args.workload, H, W)
         except Exception as e:  # the baseline must never take the GPU number down with it

@@ -1166,6 +1166,21 @@ def gen_augment():
     save("augment", **out)
 
 
+def gen_unet_imported(ref, seed=123):
+    """tests/golden/unet_imported.npz: the reference's default UNet() in train mode on a non-square 16 x 32 image, weights
+    regenerated on the test side from ``seed`` (tests/test_cpu_oracle.py::test_oracle_vs_imported_reference)."""
+    from oracle import unet as OU
+    sd = OU.make_state_dict(base_ch=64, depth=5, seed=seed)
+    m = ref.UNet()
+    m.load_state_dict(sd)
+    m.train()
+    x = torch.randn(1, 16, 32, generator=torch.Generator().manual_seed(2))
+    with torch.no_grad():
+        y = m(x)
+        close(OU.unet_forward(x, OU.clone_sd(sd), training=True), y, tol=1e-4, what="unet_imported logits")
+    save("unet_imported", x=x, y=y, seed=np.array(seed))
+
+
 def main():
     from oracle import unet as OU, losses as OL
     if "--only-augment" in sys.argv:    # needs Pillow only, not the reference
@@ -1197,6 +1212,9 @@ def main():
         return
     if "--only-finetune" in sys.argv:   # tests/golden/finetune_ref.npz alone (the reference's own TrainEpoch / ValidEpoch / train())
         gen_finetune(ref, M)
+        return
+    if "--only-unet-imported" in sys.argv:   # tests/golden/unet_imported.npz alone
+        gen_unet_imported(ref)
         return
     if "--head-worker" in sys.argv:     # (child of gen_cmunet_head_2rank)
         i = sys.argv.index("--head-worker")
@@ -1430,6 +1448,7 @@ def main():
     gen_spark(ref, S=128, ratio=0.75, name="spark_unet_m75_b8", seed=271, B=8)
     gen_optim()
     gen_cldice(M)
+    gen_unet_imported(ref)
     print("all fixtures written; oracle == reference on every case")
 
 

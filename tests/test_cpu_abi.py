@@ -90,6 +90,15 @@ def test_bench_self_launch_propagates_rank_failure():
     assert '"metric"' not in r.stdout
 
 
+def test_bench_refuses_zero_timed_steps():
+    """ms_per_step is the time of one of the --steps timed steps: a run without any is refused before anything starts."""
+    import subprocess
+    import sys
+    r = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--steps", "0"], capture_output=True, text=True, timeout=120)
+    assert r.returncode == 2 and "--steps must be at least 1" in r.stderr, r.stderr
+    assert '"metric"' not in r.stdout
+
+
 def test_conv_igemm5_kernels_use_no_scratch(tmp_path):
     """csrc/conv_igemm5.inc issues its weight / halo loads through inline asm with hand-placed s_waitcnt: hipcc does not know those registers
     are in flight, so a register SPILL right behind such a load would store (and later reload) bytes that have not arrived yet -- it happened

@@ -142,22 +142,15 @@ def test_moco_queue_semantics():
         OM.dequeue_and_enqueue(torch.randn(5, 8), queue, ptr, 32)
 
 
-@pytest.mark.skipif(not os.path.exists("/root/reference/Finetuning/model.py"), reason="reference not present (GPU box)")
-def test_oracle_vs_imported_reference():
-    """Build container only: import the reference model and compare the oracle on a fresh seeded case."""
-    import importlib.util
-    spec = importlib.util.spec_from_file_location("ref_model", "/root/reference/Finetuning/model.py")
-    ref = importlib.util.module_from_spec(spec)
-    import sys
-    sys.dont_write_bytecode = True
-    spec.loader.exec_module(ref)
-    sd = OU.make_state_dict(base_ch=64, depth=5, seed=123)
-    m = ref.UNet()
-    m.load_state_dict(sd)
-    m.train()
-    x = torch.randn(1, 16, 32, generator=torch.Generator().manual_seed(2))
+def test_oracle_vs_imported_reference(golden_dir):
+    """The oracle against what the imported reference model itself computed on a seeded non-square case
+    (tests/golden/unet_imported.npz, written by oracle/gen_golden.py: the reference's UNet() in train mode, weights by seed)."""
+    f = fx(golden_dir, "unet_imported")
+    sd = OU.make_state_dict(base_ch=64, depth=5, seed=int(f["seed"]))
+    x = f["x"]
+    assert tuple(x.shape) == (1, 16, 32) and tuple(f["y"].shape) == (1, 2, 16, 32)
     with torch.no_grad():
-        assert close(OU.unet_forward(x, OU.clone_sd(sd), training=True), m(x), 1e-4)
+        assert close(OU.unet_forward(x, OU.clone_sd(sd), training=True), f["y"], 1e-4)
 
 
 @pytest.mark.parametrize("fixture", ["spark_unet", "spark_unet_m75", "spark_unet_m75_b8"])

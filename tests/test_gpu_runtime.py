@@ -238,3 +238,46 @@ def test_mfma_sustained_rate_probe(cuda):
         assert zero > 0.97 * dense
     with pytest.raises(Exception, match="dt must be f16 or bf16"):
         ops.mfma_sustained_rate("f32", 0, iters=10, device=cuda)
+
+
+def test_bench_dump_outputs_and_full(cuda, tmp_path):
+    """bench.py at a small size, a plain run and a --full run side by side, both with --dump-outputs: the plain line holds the
+    headline only, the --full line adds the roofline, the kernel tables and the CPU baseline; both dump the same arrays (seeded inputs,
+    and the --full run's profiled pass comes after the dump), the loss being the one the line reports."""
+    import json
+    import os
+    import subprocess
+    import sys
+    root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+    argv = [sys.executable, os.path.join(root, "bench.py"), "--gpus", "1", "--steps", "3", "--warmup", "1", "--batch", "4", "--size", "128"]
+    env = {k: v for k, v in os.environ.items() if k not in ("WORLD_SIZE", "RANK", "LOCAL_RANK", "MASTER_ADDR", "MASTER_PORT", "CMU_DP_REHEARSE")}
+    runs = {"plain": [], "full": ["--full"]}
+    procs, lines = {}, {}
+    try:
+        for name, extra in runs.items():
+            procs[name] = subprocess.Popen(argv + extra + ["--dump-outputs", str(tmp_path / name)], env=env,
+                                           stdout=subprocess.PIPE, stderr=subprocess.PIPE, text=True)
+        for name, pr in procs.items():
+            so, se = pr.communicate(timeout=420)
+            assert pr.returncode == 0, se[-2000:]
+            lines[name] = json.loads([ln for ln in so.splitlines() if ln.startswith("{")][-1])
+    finally:
+        for pr in procs.values():
+            if pr.poll() is None:
+                pr.kill()
+            pr.wait()
+    plain, full = lines["plain"], lines["full"]
+    for line in (plain, full):
+        assert line["steps"] == 3 and line["unit"] == "images/sec" and line["higher_is_better"] is True and line["dtype"] == "f16"
+        assert line["ms_per_step"] > 0 and abs(line["value"] - 4 * 1000.0 / line["ms_per_step"]) <= 1e-2 * line["value"]
+    assert not any(k in plain for k in ("roofline", "kernel_ms_per_step", "step_roofline", "cpu_baseline"))
+    assert full["roofline"]["launches_per_step"] > 0 and full["kernel_ms_per_step"] and full["cpu_baseline"]["value"] > 0
+    names = sorted(os.listdir(tmp_path / "plain"))
+    assert names == sorted(os.listdir(tmp_path / "full")) and "loss.npy" in names and len(names) > 50
+    assert sum(os.path.getsize(tmp_path / "plain" / n) for n in names) <= 64 << 20
+    for n in names:
+        a, b = np.load(tmp_path / "plain" / n), np.load(tmp_path / "full" / n)
+        assert a.dtype in (np.float32, np.float64) and a.shape == b.shape and np.isfinite(a).all(), n
+        assert np.abs(a.astype(np.float64) - b).max(initial=0.0) <= 1e-6 * max(1.0, np.abs(b).max(initial=0.0)), n
+    loss = np.load(tmp_path / "plain" / "loss.npy")
+    assert loss.dtype == np.float64 and abs(loss[0] - plain["config"]["loss"]) <= 1e-5 * max(1.0, abs(loss[0]))
