@@ -30,6 +30,15 @@ _SIGS = {
     "cmu_soft_skeleton": (_I, [_P, _P, _I, _I, _I, _I, _P, _P]),
     "cmu_cldice_sums_ws_bytes": (_L, []),
     "cmu_cldice_sums": (_I, [_P, _P, _P, _P, _L, _P, _P, _P]),
+    "cmu_argmax2_mask": (_I, [_P, _I, _P, _I, _I, _I, _I, _P]),
+    "cmu_plane_mask": (_I, [_P, _I, _I, _I, _P, _I, _I, _I, _I, _P]),
+    "cmu_contour_points_ws_bytes": (_L, [_I, _I, _I]),
+    "cmu_contour_points": (_I, [_P, _P, _P, _I, _I, _I, _P, _P]),
+    "cmu_lattice_nearest_ws_bytes": (_L, [_I, _I, _I]),
+    "cmu_lattice_nearest": (_I, [_P, _P, _I, _P, _I, _I, _I, _P, _P]),
+    "cmu_skeletonize": (_I, [_P, _P, _I, _I, _I, _P]),
+    "cmu_hausdorff_finish": (_I, [_P, _P, _P, _P, _P, _P, _I, _P]),
+    "cmu_radius_finish": (_I, [_P, _P, _P, _I, _P]),
     "cmu_sgd_step": (_I, [_P, _P, _P, _P, _L, _F, _F, _F, _F, _I, _L, _F, _P]),
     "cmu_lamb_block_elems": (_I, []),
     "cmu_lamb_ws_bytes": (_L, [_I, _I]),

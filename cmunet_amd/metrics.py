@@ -7,7 +7,8 @@ and the thresholded Dice / IoU counters -- the reference makes 4-5 elementwise p
 
 Only the configuration the reference's driver uses is implemented on the HIP path (train.py:455-461:
 2 classes, activation 'softmax', threshold 0.5, ignore_channels [0], eps 1e-5 / 1e-7); other settings raise.
-``hausdorff`` / ``radius_arteries`` (CPU scikit-image / scipy geometry, metrics.py:224-395) are out of scope.
+``hausdorff`` / ``radius_arteries`` (metrics.py:224-395: scikit-image contours and skeletons, scipy KD-trees on the host) run as
+exact lattice geometry on the device (csrc/geometry.hip): no ``.cpu()``, no host sync.
 The Dice term has no gradient, exactly like the reference's thresholded version (SURVEY A-4).
 """
 import weakref
@@ -220,3 +221,181 @@ class soft_cldice(Loss):
         tprec = (s[0] + self.smooth) / (s[1] + self.smooth)
         tsens = (s[2] + self.smooth) / (s[3] + self.smooth)
         return 1. - 2.0 * (tprec * tsens) / (tprec + tsens)
+
+
+# ---------------------------------------------------------------------------------------------------
+# geometry metrics: hausdorff, radius_arteries (metrics.py:224-395) on the doubled lattice (csrc/geometry.hip)
+# ---------------------------------------------------------------------------------------------------
+def _as_masks(image, clear_border=False):
+    """(H,W) or (B,H,W) device tensor -> ((B,H,W) uint8 0/1 of ``image > 0``, batched?)."""
+    if not image.is_cuda:
+        raise RuntimeError("geometry metrics run on the GPU only (no CPU fallback)")
+    batched = image.dim() == 3
+    if image.dim() not in (2, 3):
+        raise ValueError("masks must be (H, W) or (B, H, W)")
+    x = image if batched else image.unsqueeze(0)
+    if x.dtype not in (torch.float32, torch.float64):
+        x = x.float()
+    x = x.contiguous()
+    B, H, W = x.shape
+    m = torch.empty(B, H, W, dtype=torch.uint8, device=x.device)
+    _lib.call("cmu_plane_mask", ops._p(x), int(x.dtype == torch.float64), 1, 0, ops._p(m), B, H, W, int(clear_border), ops._stream())
+    return m, batched
+
+
+def _contour_points(m):
+    """(lattice weight map (B,2H-1,2W-1) uint8, counts (B,2) int32 = (crossings, closed contours)) of find_contours(m > 0)."""
+    B, H, W = m.shape
+    wmap = torch.empty(B, 2 * H - 1, 2 * W - 1, dtype=torch.uint8, device=m.device)
+    cnt = torch.empty(B, 2, dtype=torch.int32, device=m.device)
+    ws = torch.empty(max(1, _lib.lib().cmu_contour_points_ws_bytes(B, H, W)), dtype=torch.uint8, device=m.device)
+    _lib.call("cmu_contour_points", ops._p(m), ops._p(wmap), ops._p(cnt), B, H, W, ops._p(ws), ops._stream())
+    return wmap, cnt
+
+
+def _nearest(seeds, queries, query_pixels, H, W):
+    """(B,4) fp64 (sum w*d, sum w, max d, min d): every query point's distance to the nearest seed point."""
+    B = seeds.shape[0]
+    if W > 512:
+        raise NotImplementedError(f"geometry metrics: W <= 512 (got {W})")
+    out = torch.empty(B, 4, dtype=torch.float64, device=seeds.device)
+    ws = torch.empty(_lib.lib().cmu_lattice_nearest_ws_bytes(B, H, W), dtype=torch.uint8, device=seeds.device)
+    _lib.call("cmu_lattice_nearest", ops._p(seeds), ops._p(queries), int(query_pixels), ops._p(out), B, H, W, ops._p(ws), ops._stream())
+    return out
+
+
+def _check_geometry_size(H, W):
+    if H * ((W + 31) // 32) * 32 > 512 * 512 or W > 512:
+        raise NotImplementedError(f"geometry metrics support H * W <= 512 * 512 with W <= 512 (one workgroup per image holds the "
+                                  f"bit-packed mask in LDS); got {H} x {W}")
+
+
+def skeletonize(mask):
+    """scikit-image 2-D ``skeletonize`` of (B,H,W) / (H,W) device masks (``mask > 0``) -> uint8 0/1 of the same shape."""
+    m, batched = _as_masks(mask)
+    B, H, W = m.shape
+    _check_geometry_size(H, W)
+    sk = torch.empty_like(m)
+    _lib.call("cmu_skeletonize", ops._p(m), ops._p(sk), B, H, W, ops._stream())
+    return sk if batched else sk[0]
+
+
+def contour_counts(mask):
+    """(B,2) int32 per image: (crossings, closed contours) of ``find_contours(mask > 0)``; the point count is their sum."""
+    m, batched = _as_masks(mask)
+    cnt = _contour_points(m)[1]
+    return cnt if batched else cnt[0]
+
+
+def _hausdorff_masks(a, b, modified=True, standard=True):
+    B, H, W = a.shape
+    _check_geometry_size(H, W)
+    wa, ca = _contour_points(a)
+    wb, cb = _contour_points(b)
+    fwd = _nearest(wa, wb, 0, H, W)        # every point of b to the nearest point of a (cKDTree(a).query(b))
+    bwd = _nearest(wb, wa, 0, H, W)
+    om = torch.empty(B, dtype=torch.float64, device=a.device) if modified else None
+    os_ = torch.empty(B, dtype=torch.float64, device=a.device) if standard else None
+    _lib.call("cmu_hausdorff_finish", ops._p(ca), ops._p(cb), ops._p(fwd), ops._p(bwd), ops._p(om), ops._p(os_), B, ops._stream())
+    return om, os_
+
+
+def hausdorff_distance_mask(image0, image1, method='modified'):
+    """metrics.py:224-293 on device masks ((H,W) or (B,H,W), foreground = ``> 0``): the Hausdorff distance between the contour
+    point sets of ``find_contours``, per image as fp64 (a 0-dim tensor for (H,W) inputs).  0 when both sets are empty, inf when
+    one is.  'modified' counts the repeated first point of every closed contour twice, as the reference's point arrays do."""
+    if method not in ('standard', 'modified'):
+        raise ValueError(f'unrecognized method {method}')
+    a, batched = _as_masks(image0)
+    b, _ = _as_masks(image1)
+    if a.shape != b.shape:
+        raise ValueError("both masks must have the same shape")
+    om, os_ = _hausdorff_masks(a, b, modified=method == 'modified', standard=method == 'standard')
+    out = om if method == 'modified' else os_
+    return out if batched else out[0]
+
+
+def _radius_of_masks(m):
+    """m: (B,H,W) uint8 with the border already cleared -> (B,3) fp64."""
+    B, H, W = m.shape
+    _check_geometry_size(H, W)
+    w, cnt = _contour_points(m)
+    sk = torch.empty_like(m)
+    _lib.call("cmu_skeletonize", ops._p(m), ops._p(sk), B, H, W, ops._stream())
+    near = _nearest(w, sk, 1, H, W)
+    out = torch.empty(B, 3, dtype=torch.float64, device=m.device)
+    _lib.call("cmu_radius_finish", ops._p(cnt), ops._p(near), ops._p(out), B, ops._stream())
+    return out
+
+
+def compute_radius_arteries(mask):
+    """metrics.py:378-395 on device masks ((H,W) or (B,H,W), foreground = ``> 0``): with the one-pixel border cleared, the distances
+    from every skeleton pixel to the nearest contour point -> (2 min, 2 mean, 2 max) per image, (B,3) fp64 ((3,) for an (H,W) mask).
+    (0, 0, 0) when the cleared mask has no contour.  Where the skeleton is empty but the contour is not the reference raises
+    (``np.min`` of an empty list); here that image's row is nan.  The input is not modified (the reference clears its argument)."""
+    m, batched = _as_masks(mask, clear_border=True)
+    out = _radius_of_masks(m)
+    return out if batched else out[0]
+
+
+def _check_two_class(y_pr, y_gt, what):
+    if not y_pr.is_cuda:
+        raise RuntimeError(f"{what} runs on the GPU only (no CPU fallback)")
+    if y_pr.dim() != 4 or y_pr.shape[1] != 2 or y_gt.shape != y_pr.shape:
+        raise NotImplementedError(f"{what}: two-class (B,2,H,W) logits with one-hot targets of the same shape")
+
+
+class hausdorff(Metric):
+    """metrics.py:295-331: per image, the modified Hausdorff distance between the contours of the thresholded prediction
+    (softmax, > threshold, channel 1) and of the target's channel 1; the batch value is the mean over images (inf if any image
+    is inf: one empty contour against a non-empty one).  The reference's ``torch.mean(torch.tensor(list))`` of per-image numpy
+    float64 values is an fp64 mean; so is this one.  Only the driver's configuration (train.py:463) runs on the HIP path."""
+    __name__ = "hausdorff"
+
+    def __init__(self, threshold=0.5, activation=None, ignore_channels=None, **kwargs):
+        super().__init__(**kwargs)
+        _check_cfg(activation, threshold, ignore_channels, "hausdorff")
+        self.threshold, self.ignore_channels = threshold, ignore_channels
+
+    def per_image(self, y_pr, y_gt):
+        """(B,) fp64: the reference's list ``hausdorff_distances`` (metrics.py:327-330)."""
+        _check_two_class(y_pr, y_gt, "hausdorff")
+        B, _, H, W = y_pr.shape
+        logits = y_pr.detach().float().contiguous()
+        yp = torch.empty(B, H, W, dtype=torch.float32, device=y_pr.device)
+        _lib.call("cmu_softmax2_threshold", ops._p(logits), float(self.threshold), ops._p(yp), B, H, W, ops._stream())
+        a = torch.empty(B, H, W, dtype=torch.uint8, device=y_pr.device)
+        _lib.call("cmu_plane_mask", ops._p(yp), 0, 1, 0, ops._p(a), B, H, W, 0, ops._stream())
+        gt = y_gt.detach()
+        if gt.dtype not in (torch.float32, torch.float64):
+            gt = gt.float()
+        gt = gt.contiguous()
+        g = torch.empty(B, H, W, dtype=torch.uint8, device=y_pr.device)
+        _lib.call("cmu_plane_mask", ops._p(gt), int(gt.dtype == torch.float64), 2, 1, ops._p(g), B, H, W, 0, ops._stream())
+        return _hausdorff_masks(a, g, modified=True, standard=False)[0]
+
+    def forward(self, y_pr, y_gt):
+        return self.per_image(y_pr, y_gt).mean()
+
+
+class radius_arteries(Metric):
+    """metrics.py:333-347: per image |mean radius of argmax(prediction) - mean radius of argmax(target)| (compute_radius_arteries:
+    border cleared, skeleton-to-contour distances), batch value = fp64 mean over images.  Two-class (B,2,H,W) inputs."""
+    __name__ = "radius_arteries"
+
+    def per_image(self, y_pr, y_gt):
+        """(B, 2, 3) fp64: the radius triples of prediction and target."""
+        _check_two_class(y_pr, y_gt, "radius_arteries")
+        B, _, H, W = y_pr.shape
+        m = torch.empty(2 * B, H, W, dtype=torch.uint8, device=y_pr.device)
+        for k, x in enumerate((y_pr.detach(), y_gt.detach())):
+            if x.dtype not in (torch.float32, torch.float64):
+                x = x.float()
+            x = x.contiguous()
+            _lib.call("cmu_argmax2_mask", ops._p(x), int(x.dtype == torch.float64), ops._p(m[k * B:]), B, H, W, 1, ops._stream())
+        r = _radius_of_masks(m)
+        return torch.stack((r[:B], r[B:]), 1)
+
+    def forward(self, y_pr, y_gt):
+        r = self.per_image(y_pr, y_gt)
+        return (r[:, 0, 1] - r[:, 1, 1]).abs().mean()

@@ -31,11 +31,31 @@ from . import metrics as metrics_mod
 from .model import UNet
 
 
-def _epoch_means(table):
+# columns whose epoch value follows the reference meter's running update (AverageValueMeter.add, train.py:47-66) step by step:
+# they can hold inf (an empty contour against a non-empty one), and the meter turns a column into nan once an inf is followed by
+# any further batch (inf + (x - inf) / n) -- the 'hausdorff': nan of the published logs' early epochs
+METER_COLUMNS = ("hausdorff", "radius_arteries")
+
+
+def _meter_mean(values):
+    """AverageValueMeter.mean after adding ``values`` one by one (n = 1 each)."""
+    mean = np.nan
+    with np.errstate(invalid="ignore"):
+        for k, v in enumerate(np.asarray(values, dtype=np.float64), 1):
+            mean = 0.0 + v if k == 1 else mean + (v - mean) / float(k)
+    return float(mean)
+
+
+def _epoch_means(table, names=None):
     """Mean of every column of the (batches, values) table of an epoch: the ``.mean`` the reference's per-key meters
-    hold when ``Epoch.run`` returns (train.py:129-140).  The whole table is on the host by then, so no running update."""
+    hold when ``Epoch.run`` returns (train.py:129-140).  The whole table is on the host by then, so no running update -- except
+    for the METER_COLUMNS named in ``names``, which replay the meter's recurrence (inf / nan rules included)."""
     table = np.asarray(table, dtype=np.float64)
-    return table.sum(axis=0) / table.shape[0]
+    out = table.sum(axis=0) / table.shape[0]
+    for c, name in enumerate(names or ()):
+        if name in METER_COLUMNS:
+            out[c] = _meter_mean(table[:, c])
+    return out
 
 
 class Epoch:
@@ -80,7 +100,7 @@ class Epoch:
         logs = {}
         if per_batch:
             table = torch.stack(per_batch).cpu().numpy()          # the only device -> host copy of the epoch
-            logs = {k: float(v) for k, v in zip(names, _epoch_means(table))}
+            logs = {k: float(v) for k, v in zip(names, _epoch_means(table, names))}
         if self.verbose:
             print(f"{self.stage_name}: {self._format_logs(logs)}", file=sys.stdout)
         return logs
@@ -271,12 +291,19 @@ def kfold_indices(n, n_splits=3, seed=42):
 def find_best_epochs(valid_logs_list, EPOCH, LR, BATCH, runtime, metric='dice_loss + cross_entropy_loss'):
     """utils.py:4-60: the validation logs of the epoch with the smallest ``metric`` (default: the training criterion, as there)
     plus the run's hyper-parameters.  Differences: the first epoch may be the best one (the reference leaves ``best_result``
-    unbound then and raises); 'hausdorff' / 'radius_arteries' (CPU geometry metrics, out of scope: SURVEY 2.1) are passed
-    through only when the logs hold them."""
+    unbound then and raises).  When the logs hold 'hausdorff' (metrics.hausdorff), a non-finite value of the best epoch is
+    replaced as in utils.py:36-45: by the last finite value of an earlier epoch, else None; without the key nothing changes."""
     key = metric if metric in valid_logs_list[0] else "dice_loss"
     best = min(range(len(valid_logs_list)), key=lambda i: (valid_logs_list[i][key], i))
     out = {"epochs": EPOCH, "lr": LR, "batch_size": BATCH, "runtime": runtime}
     out.update(valid_logs_list[best])
+    if "hausdorff" in valid_logs_list[best]:
+        def finite(v):
+            return v != np.inf and not np.isnan(v)
+        haus = valid_logs_list[best]["hausdorff"]
+        if not finite(haus):
+            haus = next((valid_logs_list[i]["hausdorff"] for i in range(best - 1, -1, -1) if finite(valid_logs_list[i]["hausdorff"])), None)
+        out["hausdorff"] = haus
     return out
 
 

@@ -489,6 +489,39 @@ int64_t cmu_cldice_sums_ws_bytes(void);
 int cmu_cldice_sums(const float* skel_pred, const float* y_true, const float* skel_true, const float* y_pred, int64_t n,
                     float* out4, void* ws, void* stream);
 
+/* Geometry metrics of the finetuning driver (Finetuning/train.py:462-463: hausdorff, radius_arteries; metrics.py:224-395, where
+ * scikit-image's find_contours / skeletonize and scipy KD-trees run on the host per image) as exact lattice geometry
+ * (csrc/geometry.hip).  Masks are uint8 (B,H,W) 0/1.  The doubled lattice of an H x W mask has (2H-1) x (2W-1) points: pixel
+ * centres at (even, even), crossings (midpoints of two 4-neighbour pixels that differ) at (even, odd) / (odd, even).
+ *   cmu_argmax2_mask   mask = x[:,1] > x[:,0] for (B,2,H,W) f32 / f64 x (np.argmax: ties to channel 0); clear_border zeroes the
+ *                      one-pixel image border (compute_radius_arteries, metrics.py:380-383).
+ *   cmu_plane_mask     mask = x[:,channel] > 0 for (B,C,H,W) f32 / f64 x.
+ *   cmu_contour_points wmap (B,2H-1,2W-1) uint8: the point multiset of find_contours(mask > 0) (fully_connected='low'):
+ *                      1 = a crossing, 2 = the crossing that a closed contour repeats, 0 = none; counts (B,2) int32 =
+ *                      (crossings, closed contours).  ws: cmu_contour_points_ws_bytes.
+ *   cmu_lattice_nearest for every query point, the exact distance to the nearest point of `seeds` (a wmap; distances are
+ *                      sqrt(integer)/2, bit-equal to a KD-tree's); out4 (B,4) fp64 = (sum w*d, sum w, max d, min d) over the
+ *                      queries: query_pixels = 0 -> `queries` is a wmap (weights 1 / 2), 1 -> an H x W pixel mask (weight 1 at
+ *                      (2r, 2c)).  W <= 512.  ws: cmu_lattice_nearest_ws_bytes.
+ *   cmu_skeletonize    scikit-image 2-D skeletonize (Zhang, its own 256-entry table), one workgroup per image; H * ceil(W/32) * 32
+ *                      <= 512 * 512.
+ *   cmu_hausdorff_finish  per image: 0 if both point sets are empty, inf if one is, else max of the two directed means
+ *                      (modified) / maxima (standard) (metrics.py:276-293).  Either output may be NULL.
+ *   cmu_radius_finish  per image (2 min, 2 mean, 2 max) of the skeleton-to-contour distances; (0,0,0) without a contour, nan
+ *                      when the skeleton is empty but the contour is not (the reference raises there).
+ * No host synchronisation; everything is enqueued on `stream`.                                                           */
+int cmu_argmax2_mask(const void* x, int is_f64, uint8_t* mask, int B, int H, int W, int clear_border, void* stream);
+int cmu_plane_mask(const void* x, int is_f64, int C, int channel, uint8_t* mask, int B, int H, int W, int clear_border, void* stream);
+int64_t cmu_contour_points_ws_bytes(int B, int H, int W);
+int cmu_contour_points(const uint8_t* mask, uint8_t* wmap, int* counts, int B, int H, int W, void* ws, void* stream);
+int64_t cmu_lattice_nearest_ws_bytes(int B, int H, int W);
+int cmu_lattice_nearest(const uint8_t* seeds, const uint8_t* queries, int query_pixels, double* out4, int B, int H, int W,
+                        void* ws, void* stream);
+int cmu_skeletonize(const uint8_t* mask, uint8_t* skel, int B, int H, int W, void* stream);
+int cmu_hausdorff_finish(const int* counts_a, const int* counts_b, const double* fwd4, const double* bwd4, double* out_modified,
+                         double* out_standard, int B, void* stream);
+int cmu_radius_finish(const int* counts, const double* near4, double* out3, int B, void* stream);
+
 /* Fused SGD step over a flat fp32 arena (torch.optim.SGD; MoCo: moco2_module.py:339-344, momentum 0.9, weight decay 1e-4).
  * g' = g*grad_scale + wd*p (where wd_mask != 0 or wd_mask == NULL); buf = g' on step 1, else momentum*buf + (1-dampening)*g';
  * p -= lr * (nesterov ? g' + momentum*buf : buf); momentum == 0: p -= lr*g' (buf may be NULL).                        */
