@@ -18,6 +18,7 @@ _I = ctypes.c_int
 _L = ctypes.c_int64
 _F = ctypes.c_float
 _U64 = ctypes.c_uint64
+_D = ctypes.c_double
 
 # name -> (restype, argtypes); mirrors include/cmunet_hip.h one to one.
 _SIGS = {
@@ -40,6 +41,7 @@ _SIGS = {
     "cmu_hausdorff_finish": (_I, [_P, _P, _P, _P, _P, _P, _I, _P]),
     "cmu_radius_finish": (_I, [_P, _P, _P, _I, _P]),
     "cmu_sgd_step": (_I, [_P, _P, _P, _P, _L, _F, _F, _F, _F, _I, _L, _F, _P]),
+    "cmu_sgd_step_amp": (_I, [_P, _P, _P, _P, _L, _F, _F, _F, _F, _I, _L, _F, _P, _P]),
     "cmu_lamb_block_elems": (_I, []),
     "cmu_lamb_ws_bytes": (_L, [_I, _I]),
     "cmu_resize_bicubic_ws_bytes": (_L, [_I, _I, _I, _I, _I]),
@@ -164,6 +166,16 @@ _SIGS = {
     "cmu_bn1d_bwd_colsums": (_I, [_P, _P, _P, _P, _P, _I, _P, _I, _I, _P]),
     "cmu_bn1d_relu_bwd": (_I, [_P, _P, _P, _P, _P, _P, _I, _P, _L, _P, _P, _P, _I, _I, _P]),
     "cmu_conv1x1_nchw_fwd": (_I, [_P, _L, _P, _P, _I, _P, _P, _P, _I, _I, _I, _I, _I, _I, _P]),
+    "cmu_genesis_rec_bytes": (_I, []),
+    "cmu_genesis_segments": (_I, [_I, _I]),
+    "cmu_genesis_sample": (_I, [_P, _P, _P, _I, _I, _I, _I, _I, _D, _D, _D, _D, _D, _U64, _U64, _P]),
+    "cmu_genesis_gather_shuffle": (_I, [_P, _P, _P, _P, _P, _P, _P, _I, _I, _I, _P]),
+    "cmu_genesis_bezier_ws_bytes": (_L, [_I]),
+    "cmu_genesis_bezier": (_I, [_P, _P, _I, _I, _I, _P, _P, _P]),
+    "cmu_genesis_intensity_paint": (_I, [_P, _P, _P, _U64, _U64, _P, _I, _I, _I, _P]),
+    "cmu_genesis_mae": (_I, [_P, _P, _P, _P, _P, _I, _I, _I, _P]),
+    "cmu_mse_ws_bytes": (_L, []),
+    "cmu_mse_fwd_bwd": (_I, [_P, _I, _P, _P, _P, _F, _P, _I, _I, _I, _P, _P]),
     "cmu_amp_state_bytes": (_I, []),
     "cmu_amp_init": (_I, [_P, _F, _P]),
     "cmu_amp_check_finite": (_I, [_P, _L, _P, _P]),

@@ -237,17 +237,6 @@ extern "C" int cmu_resize_nearest_u8(const uint8_t* src, int B, int Hs, int Ws, 
 // ---------------------------------------------------------------------------------------------
 // two views of a batch: ShiftPixel crops + GaussNoise on the shifted one
 // ---------------------------------------------------------------------------------------------
-__device__ static inline void philox4x32_10(uint32_t c0, uint32_t c1, uint32_t c2, uint32_t c3, uint32_t k0, uint32_t k1, uint32_t* out) {
-#pragma unroll
-    for (int r = 0; r < 10; ++r) {
-        const uint32_t hi0 = __umulhi(0xD2511F53u, c0), lo0 = 0xD2511F53u * c0;
-        const uint32_t hi1 = __umulhi(0xCD9E8D57u, c2), lo1 = 0xCD9E8D57u * c2;
-        const uint32_t n0 = hi1 ^ c1 ^ k0, n1 = lo1, n2 = hi0 ^ c3 ^ k1, n3 = lo0;
-        c0 = n0; c1 = n1; c2 = n2; c3 = n3;
-        k0 += 0x9E3779B9u; k1 += 0xBB67AE85u;
-    }
-    out[0] = c0; out[1] = c1; out[2] = c2; out[3] = c3;
-}
 // standard normal of element e: Box-Muller on the first two words of Philox(counter = (e_lo, e_hi, 0, 0), key = seed)
 __device__ static inline double aug_normal(uint64_t e, uint64_t seed) {
     uint32_t r[4];

@@ -262,3 +262,16 @@ __host__ __device__ static inline int cmu_div_up(int a, int b) { return (a + b -
 // rows per (slice, tap) of the packed 3x3 weights: [K/32B][9][npad][32 B]; 64 for narrow layers, else a multiple of 128
 __host__ __device__ static inline int cmu_conv3x3_npad(int N) { return N <= 64 ? 64 : ((N + 127) / 128) * 128; }
 static inline int64_t cmu_div_up64(int64_t a, int64_t b) { return (a + b - 1) / b; }
+
+// counter-based Philox4x32-10 (Salmon et al., SC 2011): four 32-bit words of counter (c0..c3) under key (k0, k1)
+__device__ static inline void philox4x32_10(uint32_t c0, uint32_t c1, uint32_t c2, uint32_t c3, uint32_t k0, uint32_t k1, uint32_t* out) {
+#pragma unroll
+    for (int r = 0; r < 10; ++r) {
+        const uint32_t hi0 = __umulhi(0xD2511F53u, c0), lo0 = 0xD2511F53u * c0;
+        const uint32_t hi1 = __umulhi(0xCD9E8D57u, c2), lo1 = 0xCD9E8D57u * c2;
+        const uint32_t n0 = hi1 ^ c1 ^ k0, n1 = lo1, n2 = hi0 ^ c3 ^ k1, n3 = lo0;
+        c0 = n0; c1 = n1; c2 = n2; c3 = n3;
+        k0 += 0x9E3779B9u; k1 += 0xBB67AE85u;
+    }
+    out[0] = c0; out[1] = c1; out[2] = c2; out[3] = c3;
+}

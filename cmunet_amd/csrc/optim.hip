@@ -35,6 +35,40 @@ extern "C" int cmu_sgd_step(float* p, const float* g, float* buf, const uint8_t*
     return CMU_OK;
 }
 
+// the same step under a dynamic loss scaler (cmu_amp_*): the whole step is skipped when the scaler found an inf / nan, the gradient is
+// unscaled by the scaler's current scale.  (A skipped first step leaves buf at zero: with dampening 0 the next step's
+// mom * 0 + g is the first step's clone(grad).)
+__global__ void sgd_amp_kernel(float* __restrict__ p, const float* __restrict__ g, float* __restrict__ buf, const uint8_t* __restrict__ wd_mask,
+                               int64_t n, float lr, float mom, float damp, float wd, int nesterov, int first, float gscale,
+                               const CmuAmpState* __restrict__ amp) {
+    if (amp->found_inf != 0.f) return;
+    gscale /= amp->scale;
+    for (int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; i < n; i += (int64_t)gridDim.x * blockDim.x) {
+        const float pi = p[i];
+        float gi = g[i] * gscale;
+        const float w = (wd_mask == nullptr || wd_mask[i]) ? wd : 0.f;
+        gi = fmaf(w, pi, gi);
+        float d = gi;
+        if (mom != 0.f) {
+            const float b = first ? gi : fmaf(mom, buf[i], (1.f - damp) * gi);
+            buf[i] = b;
+            d = nesterov ? fmaf(mom, b, gi) : b;
+        }
+        p[i] = fmaf(-lr, d, pi);
+    }
+}
+extern "C" int cmu_sgd_step_amp(float* p, const float* g, float* buf, const uint8_t* wd_mask, int64_t n, float lr, float momentum,
+                                float dampening, float weight_decay, int nesterov, int64_t step, float grad_scale, const void* amp_state,
+                                void* stream) {
+    CMU_CHECK_ARG(p && g && amp_state && n > 0 && step >= 1 && (momentum == 0.f || buf), "cmu_sgd_step_amp: bad args");
+    const int64_t nb = cmu_div_up64(n, 256);
+    const int grid = (int)(nb < 8192 ? nb : 8192);
+    hipLaunchKernelGGL(sgd_amp_kernel, dim3(grid), dim3(256), 0, (hipStream_t)stream, p, g, buf, wd_mask, n, lr, momentum, dampening,
+                       weight_decay, nesterov, step == 1 ? 1 : 0, grad_scale, (const CmuAmpState*)amp_state);
+    CMU_CHECK_LAUNCH("cmu_sgd_step_amp");
+    return CMU_OK;
+}
+
 // ---------------------------------------------------------------------------------------------
 // LAMB.  The arena is cut into blocks of <= LAMB_BLK elements that never straddle a parameter tensor (table built by the
 // host once): blk_start[b], blk_count[b], blk_tensor[b]; tensor t owns blocks [t_blk0[t], t_blk0[t+1]).

@@ -782,6 +782,14 @@ def sgd_step(p, g, buf, wd_mask, lr, momentum, dampening, weight_decay, nesterov
          float(weight_decay), int(nesterov), int(step), float(grad_scale), _stream())
 
 
+def sgd_step_amp(p, g, buf, wd_mask, lr, momentum, dampening, weight_decay, nesterov, step, grad_scale, amp):
+    """``sgd_step`` skipped / unscaled from the device state of ``amp`` (an ``AmpScaler``)."""
+    global PARAM_GENERATION
+    PARAM_GENERATION += 1
+    call("cmu_sgd_step_amp", _p(_f32c(p)), _p(_f32c(g)), _p(buf), _p(wd_mask), p.numel(), float(lr), float(momentum), float(dampening),
+         float(weight_decay), int(nesterov), int(step), float(grad_scale), _p(amp.state), _stream())
+
+
 def lamb_step(p, g, m, v, u, tables, lr, beta1, beta2, eps, bias_correction, grad_averaging, max_grad_norm, trust_clip,
               always_adapt, step, grad_scale, ws):
     """``tables`` = (blk_start int64, blk_count int32, blk_tensor int32, t_blk0 int32 [T+1], t_wd float32 [T]) on the device."""

@@ -332,12 +332,57 @@ class FusedSGD:
         for p in self.flat.params.values():
             p.grad = None
 
-    def step(self, grad_scale=1.0):
+    def step(self, grad_scale=1.0, amp=None):
+        """``amp``: an ``ops.AmpScaler`` -- the kernel skips the step / unscales from its device state (cmu_sgd_step_amp)."""
         if getattr(self, "auto_gather", False):      # used like a torch optimiser (Moco_v2.configure_optimizers): p.grad -> arena first
             self.flat.gather_autograd_grads()
         self.step_count += 1
+        if amp is not None:
+            ops.sgd_step_amp(self.flat.arena, self.flat.grad, self.buf, self.wd_mask, self.lr, self.momentum, self.dampening,
+                             self.weight_decay, self.nesterov, self.step_count, grad_scale, amp)
+            return
         ops.sgd_step(self.flat.arena, self.flat.grad, self.buf, self.wd_mask, self.lr, self.momentum, self.dampening,
                      self.weight_decay, self.nesterov, self.step_count, grad_scale)
+
+    def state_dict(self):
+        """torch.optim.SGD's layout: ``state[i]['momentum_buffer']`` for the i-th tensor of the arena (``model.parameters()``
+        order when the arena holds every parameter) and one ``param_groups`` entry -- what the reference saves as
+        ``optimizer_state_dict`` (Genesis_Chest_CT.py:165-169) and loads with ``optimizer.load_state_dict``."""
+        state = {}
+        if self.buf is not None and self.step_count > 0:
+            for i, n in enumerate(self.flat.names):
+                off, cnt = self.flat.offsets[n]
+                state[i] = {"momentum_buffer": self.buf[off:off + cnt].detach().view_as(self.flat.params[n]).cpu().clone()}
+        group = {"lr": self.lr, "momentum": self.momentum, "dampening": self.dampening, "weight_decay": self.weight_decay,
+                 "nesterov": bool(self.nesterov), "maximize": False, "foreach": None, "differentiable": False, "fused": None,
+                 "params": list(range(len(self.flat.names)))}
+        return {"state": state, "param_groups": [group]}
+
+    def load_state_dict(self, sd):
+        """Inverse of ``state_dict`` (also what torch.optim.SGD.state_dict() writes for the same parameter list): momentum buffers back
+        into the arena; a buffer present means the next step is not the first one (torch's ``momentum_buffer is None`` test)."""
+        groups = sd["param_groups"]
+        if len(groups) != 1 or len(groups[0]["params"]) != len(self.flat.names):
+            raise ValueError(f"optimizer state has {sum(len(g['params']) for g in groups)} parameters in {len(groups)} group(s); "
+                             f"this arena holds {len(self.flat.names)} in one")
+        g = groups[0]
+        self.lr, self.momentum, self.dampening = g["lr"], g["momentum"], g["dampening"]
+        self.weight_decay, self.nesterov = g["weight_decay"], g["nesterov"]
+        if self.momentum != 0 and self.buf is None:
+            self.buf = torch.zeros_like(self.flat.arena)
+        have = 0
+        for pos, pid in enumerate(g["params"]):
+            st = sd["state"].get(pid, {})
+            mb = st.get("momentum_buffer")
+            if mb is None:
+                continue
+            n = self.flat.names[pos]
+            off, cnt = self.flat.offsets[n]
+            if mb.numel() != cnt:
+                raise ValueError(f"momentum buffer {pid} has {mb.numel()} elements, parameter {n} {cnt}")
+            self.buf[off:off + cnt].copy_(mb.reshape(-1).to(self.buf.device, torch.float32))
+            have += 1
+        self.step_count = 1 if have else 0
 
 
 class FusedLAMB:

@@ -527,6 +527,10 @@ int cmu_radius_finish(const int* counts, const double* near4, double* out3, int 
  * p -= lr * (nesterov ? g' + momentum*buf : buf); momentum == 0: p -= lr*g' (buf may be NULL).                        */
 int cmu_sgd_step(float* p, const float* g, float* buf, const uint8_t* wd_mask, int64_t n, float lr, float momentum,
                  float dampening, float weight_decay, int nesterov, int64_t step, float grad_scale, void* stream);
+/* cmu_sgd_step under a dynamic loss scaler (amp_state, cmu_amp_*): skipped when the scaler's found_inf is set, gradients unscaled by its
+ * scale.  A skipped first step leaves buf at zero (exact for dampening 0).                                                     */
+int cmu_sgd_step_amp(float* p, const float* g, float* buf, const uint8_t* wd_mask, int64_t n, float lr, float momentum, float dampening,
+                     float weight_decay, int nesterov, int64_t step, float grad_scale, const void* amp_state, void* stream);
 
 /* Fused LAMB step (Pretraining/Spark/utils/lamb.py:67-159) over a flat fp32 arena cut into blocks of at most
  * cmu_lamb_block_elems() elements that never straddle a parameter tensor: blk_start / blk_count / blk_tensor [nblocks]
@@ -627,6 +631,39 @@ int cmu_bn1d_relu_bwd(const float* dy, const float* x, const float* y, const flo
  * slices, H*W % 4 == 0.                                                                                                   */
 int cmu_conv1x1_nchw_fwd(const void* x, int64_t ldx, const float* in_scale, const float* in_shift, int relu_from, const float* w,
                          const float* bias, float* out, int B, int H, int W, int K, int N, int dt, void* stream);
+
+/* ---------------------------------------------------------------------------------------------
+ * Models Genesis / MAE baseline pretraining inputs (csrc/genesis.hip; Pretraining/Transformation_based/utils.py:69-253)
+ * ------------------------------------------------------------------------------------------- */
+/* One 112-byte record per image (layout: genesis.hip GenesisRec, mirrored by cmunet_amd/genesis.py REC_DTYPE) is the contract
+ * between the randomness (this device sampler, or the host replay of the reference's own random / numpy streams) and the apply
+ * kernels.  blocks: int16 (x0, y0, bx, by) x 10,000 per image; perms: uint8, (H/25)*(W/25) bytes per block.                  */
+int cmu_genesis_rec_bytes(void);
+/* row segments of the gather pass's LDS owner map (= min / max partials per image)                                          */
+int cmu_genesis_segments(int H, int W);
+/* Philox4x32-10 keyed by (seed, offset): batch selection (B distinct of N, uniform order) and, unless mae, the Genesis record
+ * with the reference's laws (3-flip loop, local / non-linear / paint branches, truncated-geometric rectangle counts, uniform
+ * Fisher-Yates per block).  42 <= H, W and (H/25)*(W/25) <= 256 for Genesis; B <= min(N, 1024).                              */
+int cmu_genesis_sample(void* recs, int16_t* blocks, uint8_t* perms, int N, int B, int H, int W, int mae, double flip_rate,
+                       double local_rate, double nonlinear_rate, double paint_rate, double inpaint_rate, uint64_t seed,
+                       uint64_t offset, void* stream);
+/* y = flip(src[rec.src]) (src (N,H,W) f32); x = local pixel shuffle of y (last covering block wins); minmax (B, segments, 2) f32 */
+int cmu_genesis_gather_shuffle(const float* src, const void* recs, const int16_t* blocks, const uint8_t* perms, float* x, float* y,
+                               float* minmax, int B, int H, int W, void* stream);
+/* both sampled cubics of nonlinear_transformation (fp64, 100,000 points) and their sorted copies in ws; a cubic whose samples show
+ * more than 16 monotone runs sets bit 0 of *err, a rank outside the table bit 1 (device word, read at the next synchronisation). */
+int64_t cmu_genesis_bezier_ws_bytes(int B);
+int cmu_genesis_bezier(const void* recs, const float* minmax, int B, int H, int W, void* ws, int* err, void* stream);
+/* x <- np.interp(x, xs, ys) (fp64) where the record asks for it, then in- / out-painting; noise (B,H,W) f32 or NULL (Philox).  */
+int cmu_genesis_intensity_paint(const void* recs, const void* ws, const float* noise, uint64_t seed, uint64_t offset, float* x, int B,
+                                int H, int W, void* stream);
+/* generate_pair_mae: y = src[rec.src], x = y * (1 - mask) with mask (H,W) uint8 shared by the batch                           */
+int cmu_genesis_mae(const float* src, const void* recs, const uint8_t* mask, float* x, float* y, int B, int H, int W, void* stream);
+/* nn.MSELoss()(logits[:,0], y) over B*H*W into loss (1 fp32); dlogits (nullable) = d loss * loss_scale [* amp scale] / d logits
+ * (zero on channels > 0).  Fixed-order reduction: same inputs, same bits.  ws: cmu_mse_ws_bytes().                           */
+int64_t cmu_mse_ws_bytes(void);
+int cmu_mse_fwd_bwd(const float* logits, int K, const float* y, float* loss, float* dlogits, float loss_scale, const void* amp_state,
+                    int B, int H, int W, void* ws, void* stream);
 
 /* Measurement support (bench.py's roofline block; no reference counterpart): the 16-bit MFMA rate this chip SUSTAINS.
  * Every wave of a one-workgroup-per-CU grid issues iters x 8 back-to-back 32x32x16 MFMAs from registers (no LDS, no
