@@ -174,6 +174,13 @@ _SIGS = {
     "cmu_genesis_bezier": (_I, [_P, _P, _I, _I, _I, _P, _P, _P]),
     "cmu_genesis_intensity_paint": (_I, [_P, _P, _P, _U64, _U64, _P, _I, _I, _I, _P]),
     "cmu_genesis_mae": (_I, [_P, _P, _P, _P, _P, _I, _I, _I, _P]),
+    "cmu_ftaug_rec_layout": (_I, [_P, _I]),
+    "cmu_ftaug_max_ksize": (_I, []),
+    "cmu_ftaug_sample": (_I, [_P, _I, _I, _I, _I, _P, _I, _U64, _U64, _P]),
+    "cmu_ftaug_photometric": (_I, [_P, _I, _I, _I, _P, _P, _U64, _U64, _I, _P, _I, _P]),
+    "cmu_ftaug_apply": (_I, [_P, _P, _I, _I, _I, _P, _P, _U64, _U64, _I, _P, _P, _I, _P]),
+    "cmu_ftaug_resize_ws_bytes": (_L, [_I, _I, _I]),
+    "cmu_ftaug_resize_onehot": (_I, [_P, _P, _I, _I, _I, _P, _P, _U64, _U64, _I, _P, _I, _P, _P, _I, _I, _P, _P]),
     "cmu_mse_ws_bytes": (_L, []),
     "cmu_mse_fwd_bwd": (_I, [_P, _I, _P, _P, _P, _F, _P, _I, _I, _I, _P, _P]),
     "cmu_amp_state_bytes": (_I, []),

@@ -17,47 +17,12 @@
 //                         generator in the kernel (no 8-byte-per-pixel read; one workgroup per sample).
 // All three are HBM-bound single passes over a few MB; nothing here is on the bench's timed path.
 #include "common.h"
+#include "pillow_resample.h"
 #include <math.h>
 // hipcc contracts a*b + c into an FMA by default (-ffp-contract=fast), through the __d*_rn intrinsics too (they are plain
 // operators in the HIP headers) and past this pragma: one rounding instead of two, i.e. a handful of results per image 1 ulp
 // off Pillow's.  The Makefile compiles this file with -ffp-contract=off; tests/test_gpu_augment.py would catch a build without.
 #pragma clang fp contract(off)
-
-__device__ static inline double aug_cubic(double x) {
-    // Pillow bicubic_filter with a = -0.5: ((a+2)x - (a+3))x^2 + 1 on [0,1), (((x-5)x + 8)x - 4)a on [1,2)
-    x = fabs(x);
-    if (x < 1.0) return __dadd_rn(__dmul_rn(__dmul_rn(__dadd_rn(__dmul_rn(1.5, x), -2.5), x), x), 1.0);
-    if (x < 2.0) return __dmul_rn(__dadd_rn(__dmul_rn(__dadd_rn(__dmul_rn(__dadd_rn(x, -5.0), x), 8.0), x), -4.0), -0.5);
-    return 0.0;
-}
-
-struct AugWin {
-    int xmin, count;
-    double center, ss, ww;
-};
-// the window and the normalisation sum of output index xx for a resize in_size -> out_size
-__device__ static inline AugWin aug_window(int xx, int in_size, int out_size) {
-    AugWin w;
-    const double scale = __ddiv_rn((double)in_size, (double)out_size);
-    const double filterscale = scale < 1.0 ? 1.0 : scale;
-    const double support = __dmul_rn(2.0, filterscale);
-    w.ss = __ddiv_rn(1.0, filterscale);
-    w.center = __dmul_rn(__dadd_rn((double)xx, 0.5), scale);
-    int xmin = (int)__dadd_rn(__dadd_rn(w.center, -support), 0.5);
-    if (xmin < 0) xmin = 0;
-    int xmax = (int)__dadd_rn(__dadd_rn(w.center, support), 0.5);
-    if (xmax > in_size) xmax = in_size;
-    w.xmin = xmin;
-    w.count = xmax - xmin;
-    double ww = 0.0;
-    for (int x = 0; x < w.count; ++x) ww = __dadd_rn(ww, aug_cubic(__dmul_rn(__dadd_rn(__dadd_rn((double)(x + xmin), -w.center), 0.5), w.ss)));
-    w.ww = ww;
-    return w;
-}
-__device__ static inline double aug_coeff(const AugWin& w, int x) {
-    const double k = aug_cubic(__dmul_rn(__dadd_rn(__dadd_rn((double)(x + w.xmin), -w.center), 0.5), w.ss));
-    return w.ww != 0.0 ? __ddiv_rn(k, w.ww) : k;
-}
 
 // horizontal pass: tmp[b][y][xx] for the rows of the crop window; y indexes rows of the window
 __global__ void resize_h_kernel(const float* __restrict__ src, int Hs, int Ws, const int* __restrict__ boxes, float* __restrict__ tmp,

@@ -659,6 +659,49 @@ int cmu_genesis_intensity_paint(const void* recs, const void* ws, const float* n
                                 int H, int W, void* stream);
 /* generate_pair_mae: y = src[rec.src], x = y * (1 - mask) with mask (H,W) uint8 shared by the batch                           */
 int cmu_genesis_mae(const float* src, const void* recs, const uint8_t* mask, float* x, float* y, int B, int H, int W, void* stream);
+/* ---------------------------------------------------------------------------------------------
+ * Finetuning training augmentation (csrc/ft_augment.hip; Finetuning/dataset.py:134-165 get_training_augmentation, then the
+ * SegmentationDataset resize + one-hot of dataset.py:44-55).  DESIGN.md 4.13 restates the rules.
+ * ------------------------------------------------------------------------------------------- */
+/* One record per image holds every random decision of its augmentation (mirrored by cmunet_amd/ft_augment.py REC_DTYPE; the
+ * layout query below lets the host check it).  ops: bit 0 GaussNoise, 1 GaussianBlur, 2 RandomBrightnessContrast, 3 Downscale,
+ * 4 OneOf; oneof: 0 HorizontalFlip, 1 VerticalFlip, 2 RandomRotate90 (np.rot90 by rot_k), 3 GaussNoise.                         */
+typedef struct CmuFtAugRec {
+    int32_t ops;
+    int32_t y0, x0;         /* RandomCrop offset (row, column)                                                              */
+    int32_t ksize;          /* GaussianBlur kernel size (odd)                                                               */
+    double var_noise;       /* GaussNoise variance                                                                          */
+    double var_oneof;       /* OneOf's GaussNoise variance                                                                  */
+    double sigma;           /* GaussianBlur sigma                                                                           */
+    double alpha, beta;     /* RandomBrightnessContrast: out = img * alpha + beta                                           */
+    double scale;           /* Downscale factor                                                                             */
+    int32_t oneof, rot_k;
+} CmuFtAugRec;              /* 72 bytes */
+/* out[0] = sizeof(CmuFtAugRec), out[1..12] = the fields' offsets in declaration order; returns the count (13)                */
+int cmu_ftaug_rec_layout(int64_t* out, int n);
+/* the largest GaussianBlur kernel size the photometric pass takes (its LDS halo is sized for it)                              */
+int cmu_ftaug_max_ksize(void);
+/* B records, Philox4x32-10 keyed by (seed, offset).  params (host, nparams = 19): p_noise, var lo, hi; p_blur, ksize lo, hi,
+ * sigma lo, hi; p_brightness_contrast, brightness lo, hi, contrast lo, hi; p_downscale, scale lo, hi; p_oneof, var lo, hi.
+ * crop <= H, W.  Every parameter is drawn whether or not its transform fires.                                                 */
+int cmu_ftaug_sample(void* recs, int B, int H, int W, int crop, const double* params, int nparams, uint64_t seed, uint64_t offset,
+                     void* stream);
+/* P (B,S,S) f32 = brightness / contrast (float32, [0,1] clip if clip) of the separable Gaussian blur (float64 taps, reflect-101)
+ * of GaussNoise (float64, clip if clip) of the S x S crop of src (B,H,W) f32.  noise: (2,B,S,S) float64 standard normals (plane 0
+ * is read here) or NULL for Philox keyed by (seed, offset, image, pixel).                                                      */
+int cmu_ftaug_photometric(const float* src, int B, int H, int W, const void* recs, const double* noise, uint64_t seed, uint64_t offset,
+                          int clip, float* out, int S, void* stream);
+/* the augmented image and mask before the resize: img_out = OneOf(Downscale(P)) (plane 1 of noise for OneOf's GaussNoise),
+ * mask_out = OneOf's geometry of the crop of masks (B,H,W) uint8; both (B,S,S)                                                  */
+int cmu_ftaug_apply(const float* aug, const uint8_t* masks, int B, int H, int W, const void* recs, const double* noise, uint64_t seed,
+                    uint64_t offset, int clip, float* img_out, uint8_t* mask_out, int S, void* stream);
+/* the same, composed into the Pillow bicubic resize to size x size (img_out (B,size,size) f32, bit-equal to cmu_resize_bicubic of
+ * the materialised image) and the NEAREST resize + one-hot of the mask (onehot (B,ncls,size,size) float64, class_values a host
+ * array of ncls <= 16 values).  ws: cmu_ftaug_resize_ws_bytes(B, S, size).                                                      */
+int64_t cmu_ftaug_resize_ws_bytes(int B, int S, int size);
+int cmu_ftaug_resize_onehot(const float* aug, const uint8_t* masks, int B, int H, int W, const void* recs, const double* noise,
+                            uint64_t seed, uint64_t offset, int clip, const int* class_values, int ncls, float* img_out, double* onehot,
+                            int S, int size, void* ws, void* stream);
 /* nn.MSELoss()(logits[:,0], y) over B*H*W into loss (1 fp32); dlogits (nullable) = d loss * loss_scale [* amp scale] / d logits
  * (zero on channels > 0).  Fixed-order reduction: same inputs, same bits.  ws: cmu_mse_ws_bytes().                           */
 int64_t cmu_mse_ws_bytes(void);
