@@ -579,6 +579,8 @@ __global__ __launch_bounds__(256) void amp_check_kernel(const float* __restrict_
     if (blockIdx.x == 0 && threadIdx.x < (n & 3)) bad |= !(fabsf(g[(n4 << 2) + threadIdx.x]) <= 3.4028234664e38f);
     if (__any(bad) && (threadIdx.x & 63) == 0) s->found_inf = 1.f;     // every writer stores the same value
 }
+// torch._amp_update_scale_: a growth whose product is not finite keeps the old scale (an inf scale would overflow every gradient and
+// skip every later step, with backoff unable to bring it down); the tracker restarts either way
 __global__ void amp_update_kernel(CmuAmpState* s, float growth, float backoff, int interval) {
     if (s->found_inf != 0.f) {
         s->scale *= backoff;
@@ -587,7 +589,8 @@ __global__ void amp_update_kernel(CmuAmpState* s, float growth, float backoff, i
     } else {
         s->good_steps += 1;
         if (++s->growth_tracker == interval) {
-            s->scale *= growth;
+            const float grown = s->scale * growth;
+            if (fabsf(grown) <= 3.4028234664e38f) s->scale = grown;
             s->growth_tracker = 0;
         }
     }

@@ -36,12 +36,13 @@ extern "C" int cmu_sgd_step(float* p, const float* g, float* buf, const uint8_t*
 }
 
 // the same step under a dynamic loss scaler (cmu_amp_*): the whole step is skipped when the scaler found an inf / nan, the gradient is
-// unscaled by the scaler's current scale.  (A skipped first step leaves buf at zero: with dampening 0 the next step's
-// mom * 0 + g is the first step's clone(grad).)
+// unscaled by the scaler's current scale.  The first update is the first one the scaler lets through (good_steps == 0), not the host's
+// step 1: torch.optim.SGD never runs behind a skipped step, so its buffer is still unset there and it takes buf = clone(grad).
 __global__ void sgd_amp_kernel(float* __restrict__ p, const float* __restrict__ g, float* __restrict__ buf, const uint8_t* __restrict__ wd_mask,
-                               int64_t n, float lr, float mom, float damp, float wd, int nesterov, int first, float gscale,
+                               int64_t n, float lr, float mom, float damp, float wd, int nesterov, float gscale,
                                const CmuAmpState* __restrict__ amp) {
     if (amp->found_inf != 0.f) return;
+    const bool first = amp->good_steps == 0;
     gscale /= amp->scale;
     for (int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; i < n; i += (int64_t)gridDim.x * blockDim.x) {
         const float pi = p[i];
@@ -64,7 +65,7 @@ extern "C" int cmu_sgd_step_amp(float* p, const float* g, float* buf, const uint
     const int64_t nb = cmu_div_up64(n, 256);
     const int grid = (int)(nb < 8192 ? nb : 8192);
     hipLaunchKernelGGL(sgd_amp_kernel, dim3(grid), dim3(256), 0, (hipStream_t)stream, p, g, buf, wd_mask, n, lr, momentum, dampening,
-                       weight_decay, nesterov, step == 1 ? 1 : 0, grad_scale, (const CmuAmpState*)amp_state);
+                       weight_decay, nesterov, grad_scale, (const CmuAmpState*)amp_state);
     CMU_CHECK_LAUNCH("cmu_sgd_step_amp");
     return CMU_OK;
 }

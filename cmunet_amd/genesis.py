@@ -392,7 +392,7 @@ def pretrain_genesis(config, images_train, images_valid, model=None, seed=0, ref
     tr = GenesisPretrainer(model, lr=1e-2, momentum=0.9, weight_decay=0.0, nesterov=False, patience=conf.patience)
     initial_epoch = 0
     if conf.weights is not None:
-        tr.opt.load_state_dict(ck["optimizer_state_dict"])
+        tr.opt.load_state_dict(ck["optimizer_state_dict"], amp=tr.amp)
         initial_epoch = int(ck["epoch"])
         log(f"Loading weights from {conf.weights}")
     ops.bump_param_generation()

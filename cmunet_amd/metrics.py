@@ -204,19 +204,16 @@ class soft_cldice(Loss):
         B, K, H, W = y_pred.shape
         if K != 2:
             raise NotImplementedError("soft_cldice: two-class logits expected")
-        lib = _lib.lib()
         logits = y_pred.detach().float().contiguous()
         yt = y_true[:, 1].detach().float().contiguous()
         yp = torch.empty(B, H, W, dtype=torch.float32, device=y_pred.device)
-        _lib.call("cmu_softmax2_threshold", ops._p(logits), self.threshold, ops._p(yp), B, H, W, ops._stream())
-        n = B * H * W
-        ws = torch.empty(lib.cmu_soft_skeleton_ws_bytes(n), dtype=torch.uint8, device=y_pred.device)
+        ops.softmax2_threshold(logits, self.threshold, yp)
+        ws = torch.empty(_lib.lib().cmu_soft_skeleton_ws_bytes(B * H * W), dtype=torch.uint8, device=y_pred.device)
         sp, st = torch.empty_like(yp), torch.empty_like(yp)
-        _lib.call("cmu_soft_skeleton", ops._p(yp), ops._p(sp), B, H, W, self.num_iter, ops._p(ws), ops._stream())
-        _lib.call("cmu_soft_skeleton", ops._p(yt), ops._p(st), B, H, W, self.num_iter, ops._p(ws), ops._stream())
+        ops.soft_skeleton(yp, sp, self.num_iter, ws)
+        ops.soft_skeleton(yt, st, self.num_iter, ws)
         out4 = torch.empty(4, dtype=torch.float32, device=y_pred.device)
-        ws2 = torch.empty(lib.cmu_cldice_sums_ws_bytes(), dtype=torch.uint8, device=y_pred.device)
-        _lib.call("cmu_cldice_sums", ops._p(sp), ops._p(yt), ops._p(st), ops._p(yp), n, ops._p(out4), ops._p(ws2), ops._stream())
+        ops.cldice_sums(sp, yt, st, yp, out4)
         s = out4.double()
         tprec = (s[0] + self.smooth) / (s[1] + self.smooth)
         tsens = (s[2] + self.smooth) / (s[3] + self.smooth)
@@ -363,7 +360,7 @@ class hausdorff(Metric):
         B, _, H, W = y_pr.shape
         logits = y_pr.detach().float().contiguous()
         yp = torch.empty(B, H, W, dtype=torch.float32, device=y_pr.device)
-        _lib.call("cmu_softmax2_threshold", ops._p(logits), float(self.threshold), ops._p(yp), B, H, W, ops._stream())
+        ops.softmax2_threshold(logits, self.threshold, yp)
         a = torch.empty(B, H, W, dtype=torch.uint8, device=y_pr.device)
         _lib.call("cmu_plane_mask", ops._p(yp), 0, 1, 0, ops._p(a), B, H, W, 0, ops._stream())
         gt = y_gt.detach()

@@ -475,6 +475,29 @@ def scale_by_device_scalar(v, s):
     call("cmu_scale_by_device_scalar", _p(v), _p(_f32c(s.reshape(-1))), v.numel(), _stream())
 
 
+def softmax2_threshold(logits, threshold, out):
+    """out (B,H,W) fp32 = (softmax(logits, 1)[:, 1] > threshold) for (B,2,H,W) fp32 logits."""
+    B, K, H, W = logits.shape
+    assert K == 2 and out.shape == (B, H, W)
+    call("cmu_softmax2_threshold", _p(_f32c(logits)), float(threshold), _p(_f32c(out)), B, H, W, _stream())
+
+
+def soft_skeleton(img, skel, num_iter, ws=None):
+    """skel = the soft skeleton of the fp32 (planes, H, W) stack ``img`` after ``num_iter`` rounds (metrics.py:448-490)."""
+    P, H, W = img.shape
+    if ws is None:
+        ws = torch.empty(_lib.lib().cmu_soft_skeleton_ws_bytes(img.numel()), dtype=torch.uint8, device=img.device)
+    call("cmu_soft_skeleton", _p(_f32c(img)), _p(_f32c(skel)), P, H, W, int(num_iter), _p(ws), _stream())
+
+
+def cldice_sums(skel_pred, y_true, skel_true, y_pred, out4, ws=None):
+    """out4 = (sum skel_pred*y_true, sum skel_pred, sum skel_true*y_pred, sum skel_true) over same-sized fp32 tensors."""
+    if ws is None:
+        ws = torch.empty(_lib.lib().cmu_cldice_sums_ws_bytes(), dtype=torch.uint8, device=skel_pred.device)
+    call("cmu_cldice_sums", _p(_f32c(skel_pred)), _p(_f32c(y_true)), _p(_f32c(skel_true)), _p(_f32c(y_pred)), skel_pred.numel(),
+         _p(out4), _p(ws), _stream())
+
+
 # ------------------------------------------------------------------------------------------------
 # SparK sparse ops
 # ------------------------------------------------------------------------------------------------

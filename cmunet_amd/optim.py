@@ -327,29 +327,39 @@ class FusedSGD:
         self.buf = torch.zeros_like(flat.arena) if momentum != 0 else None
         self.wd_mask = flat.wd_mask(decay_filter) if (decay_filter is not None and weight_decay != 0.0) else None
         self.step_count = 0
+        self.amp = None          # the ops.AmpScaler the steps run under (set by the first step(amp=...))
 
     def zero_grad(self, set_to_none=True):
         for p in self.flat.params.values():
             p.grad = None
 
     def step(self, grad_scale=1.0, amp=None):
-        """``amp``: an ``ops.AmpScaler`` -- the kernel skips the step / unscales from its device state (cmu_sgd_step_amp)."""
+        """``amp``: an ``ops.AmpScaler`` -- the kernel skips the step / unscales from its device state (cmu_sgd_step_amp), and the
+        first update that initialises the momentum buffer is the first one the scaler lets through (its ``good_steps`` == 0)."""
         if getattr(self, "auto_gather", False):      # used like a torch optimiser (Moco_v2.configure_optimizers): p.grad -> arena first
             self.flat.gather_autograd_grads()
         self.step_count += 1
         if amp is not None:
+            self.amp = amp
             ops.sgd_step_amp(self.flat.arena, self.flat.grad, self.buf, self.wd_mask, self.lr, self.momentum, self.dampening,
                              self.weight_decay, self.nesterov, self.step_count, grad_scale, amp)
             return
         ops.sgd_step(self.flat.arena, self.flat.grad, self.buf, self.wd_mask, self.lr, self.momentum, self.dampening,
                      self.weight_decay, self.nesterov, self.step_count, grad_scale)
 
+    def updates_taken(self):
+        """Whether an update has reached the momentum buffer: under a loss scaler only its ``good_steps`` knows (synchronises)."""
+        if self.amp is not None:
+            return self.amp.read()[3] > 0
+        return self.step_count > 0
+
     def state_dict(self):
         """torch.optim.SGD's layout: ``state[i]['momentum_buffer']`` for the i-th tensor of the arena (``model.parameters()``
         order when the arena holds every parameter) and one ``param_groups`` entry -- what the reference saves as
-        ``optimizer_state_dict`` (Genesis_Chest_CT.py:165-169) and loads with ``optimizer.load_state_dict``."""
+        ``optimizer_state_dict`` (Genesis_Chest_CT.py:165-169) and loads with ``optimizer.load_state_dict``.  No momentum state
+        before the first update actually taken (steps skipped by the loss scaler do not count), as torch.optim.SGD has none."""
         state = {}
-        if self.buf is not None and self.step_count > 0:
+        if self.buf is not None and self.updates_taken():
             for i, n in enumerate(self.flat.names):
                 off, cnt = self.flat.offsets[n]
                 state[i] = {"momentum_buffer": self.buf[off:off + cnt].detach().view_as(self.flat.params[n]).cpu().clone()}
@@ -358,9 +368,11 @@ class FusedSGD:
                  "params": list(range(len(self.flat.names)))}
         return {"state": state, "param_groups": [group]}
 
-    def load_state_dict(self, sd):
+    def load_state_dict(self, sd, amp=None):
         """Inverse of ``state_dict`` (also what torch.optim.SGD.state_dict() writes for the same parameter list): momentum buffers back
-        into the arena; a buffer present means the next step is not the first one (torch's ``momentum_buffer is None`` test)."""
+        into the arena; a buffer present means the next step is not the first one (torch's ``momentum_buffer is None`` test).
+        ``amp``: the scaler the resumed steps will run under (defaults to the one already attached) -- its ``good_steps`` decides the
+        first update, so a loaded buffer raises it to at least 1."""
         groups = sd["param_groups"]
         if len(groups) != 1 or len(groups[0]["params"]) != len(self.flat.names):
             raise ValueError(f"optimizer state has {sum(len(g['params']) for g in groups)} parameters in {len(groups)} group(s); "
@@ -383,6 +395,13 @@ class FusedSGD:
             self.buf[off:off + cnt].copy_(mb.reshape(-1).to(self.buf.device, torch.float32))
             have += 1
         self.step_count = 1 if have else 0
+        amp = amp if amp is not None else self.amp
+        if amp is not None:
+            self.amp = amp
+            cur = amp.state_dict()
+            if have and cur["good_steps"] == 0:
+                cur["good_steps"] = 1
+                amp.load_state_dict(cur)
 
 
 class FusedLAMB:

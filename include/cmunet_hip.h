@@ -473,7 +473,8 @@ int cmu_adam_ema_step(float* p, const float* g, float* m, float* v, const uint8_
  * int32 skipped_steps, pad): no host synchronisation per step.  Per step: the loss kernel scales its gradient by
  * state.scale; after the gradient exchange cmu_amp_check_finite raises found_inf if any gradient is inf / nan; the
  * optimiser kernel skips or unscales (see cmu_adam_step); cmu_amp_update halves the scale after a skipped step or doubles
- * it after growth_interval clean ones, and clears found_inf.                                                      */
+ * it after growth_interval clean ones (keeping it when the product is not finite, as torch._amp_update_scale_ does), and
+ * clears found_inf.                                                                                               */
 int cmu_amp_state_bytes(void);
 int cmu_amp_init(void* state, float init_scale, void* stream);
 int cmu_amp_check_finite(const float* g, int64_t n, void* state, void* stream);
@@ -528,7 +529,8 @@ int cmu_radius_finish(const int* counts, const double* near4, double* out3, int 
 int cmu_sgd_step(float* p, const float* g, float* buf, const uint8_t* wd_mask, int64_t n, float lr, float momentum,
                  float dampening, float weight_decay, int nesterov, int64_t step, float grad_scale, void* stream);
 /* cmu_sgd_step under a dynamic loss scaler (amp_state, cmu_amp_*): skipped when the scaler's found_inf is set, gradients unscaled by its
- * scale.  A skipped first step leaves buf at zero (exact for dampening 0).                                                     */
+ * scale.  The first update (buf = g') is the first one the scaler lets through -- its good_steps == 0 -- whatever ``step`` says, as
+ * torch.optim.SGD never runs behind a skipped step.                                                                              */
 int cmu_sgd_step_amp(float* p, const float* g, float* buf, const uint8_t* wd_mask, int64_t n, float lr, float momentum, float dampening,
                      float weight_decay, int nesterov, int64_t step, float grad_scale, const void* amp_state, void* stream);
 
