@@ -181,6 +181,12 @@ _SIGS = {
     "cmu_ftaug_apply": (_I, [_P, _P, _I, _I, _I, _P, _P, _U64, _U64, _I, _P, _P, _I, _P]),
     "cmu_ftaug_resize_ws_bytes": (_L, [_I, _I, _I]),
     "cmu_ftaug_resize_onehot": (_I, [_P, _P, _I, _I, _I, _P, _P, _U64, _U64, _I, _P, _I, _P, _P, _I, _I, _P, _P]),
+    "cmu_mocoviews_rec_layout": (_I, [_P, _I]),
+    "cmu_mocoviews_max_ksize": (_I, []),
+    "cmu_mocoviews_sample": (_I, [_P, _I, _I, _I, _P, _I, _U64, _U64, _P]),
+    "cmu_mocoviews_geometry": (_I, [_P, _I, _I, _I, _P, _I, _I, _I, _P, _I, _P, _P]),
+    "cmu_mocoviews_max": (_I, [_P, _P, _I, _P]),
+    "cmu_mocoviews_noise": (_I, [_P, _I, _I, _P, _P, _P, _U64, _U64, _P]),
     "cmu_mse_ws_bytes": (_L, []),
     "cmu_mse_fwd_bwd": (_I, [_P, _I, _P, _P, _P, _F, _P, _I, _I, _I, _P, _P]),
     "cmu_amp_state_bytes": (_I, []),

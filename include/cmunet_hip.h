@@ -704,6 +704,39 @@ int64_t cmu_ftaug_resize_ws_bytes(int B, int S, int size);
 int cmu_ftaug_resize_onehot(const float* aug, const uint8_t* masks, int B, int H, int W, const void* recs, const double* noise,
                             uint64_t seed, uint64_t offset, int clip, const int* class_values, int ncls, float* img_out, double* onehot,
                             int S, int size, void* ws, void* stream);
+/* ---------------------------------------------------------------------------------------------
+ * MoCo-v2's two augmented views (csrc/moco_views.hip; Pretraining/MoCo/.../moco_data_module.py:119-132 tau_g, torchvision 0.14.0's
+ * tensor path).  DESIGN.md 4.14 restates the rules.
+ * ------------------------------------------------------------------------------------------- */
+/* One record per (image, view) holds every random decision (mirrored by cmunet_amd/moco_views.py REC_DTYPE; records are laid out
+ * (B, 2)).  ops: bit 0 RandomRotation, 1 GaussianBlur, 2 horizontal flip, 3 vertical flip, 4 GaussNoise.                          */
+typedef struct CmuMocoViewRec {
+    int32_t ops;
+    int32_t top, left, height, width;   /* RandomResizedCrop's box (i, j, h, w)                                                 */
+    int32_t pad;
+    double angle;                       /* RandomRotation angle in degrees                                                      */
+    double sigma;                       /* GaussianBlur sigma (both axes)                                                       */
+} CmuMocoViewRec;                       /* 40 bytes */
+/* out[0] = sizeof(CmuMocoViewRec), out[1..7] = the offsets of ops, top, left, height, width, angle, sigma; returns the count (8) */
+int cmu_mocoviews_rec_layout(int64_t* out, int n);
+/* the largest GaussianBlur kernel size (either axis) the geometry pass takes (its LDS halo is sized for it)                       */
+int cmu_mocoviews_max_ksize(void);
+/* 2 * B records, Philox4x32-10 keyed by (seed, offset).  params (host, nparams = 12): p_rotation, degrees; scale lo, hi, ratio lo,
+ * hi; p_blur, sigma lo, hi; p_hflip; p_vflip; p_noise.  The crop's rejection loop (10 attempts, then the centred box) runs in the
+ * kernel.  Every parameter is drawn whether or not its transform fires.                                                           */
+int cmu_mocoviews_sample(void* recs, int B, int H, int W, const double* params, int nparams, uint64_t seed, uint64_t offset,
+                         void* stream);
+/* out (2,B,O,O) f32 = flips(blur(resize(crop(rotate(src (B,H,W) f32))))) of view v of image b at out[v][b]: rotation NEAREST about
+ * the centre with zero fill, bilinear resize (antialias: ATen's triangle filter), kx x ky Gaussian blur with reflect padding.
+ * vmax: 2 * B words, zeroed here and then merged with every view's maximum (order-preserving bits; cmu_mocoviews_max decodes).   */
+int cmu_mocoviews_geometry(const float* src, int B, int H, int W, const void* recs, int kx, int ky, int antialias, float* out, int O,
+                           void* vmax, void* stream);
+/* out (B,2) f32 = the maxima that cmu_mocoviews_geometry left in vmax                                                            */
+int cmu_mocoviews_max(const void* vmax, float* out, int B, void* stream);
+/* GaussNoise on the views whose record asks for it: out += (max / 10) * z, float32; noise (2,B,O,O) f32 standard normals or NULL for
+ * Philox keyed by (seed, offset, view, pixel).  Reads the maxima from vmax: no host round trip.                                   */
+int cmu_mocoviews_noise(float* out, int B, int O, const void* recs, const void* vmax, const float* noise, uint64_t seed,
+                        uint64_t offset, void* stream);
 /* nn.MSELoss()(logits[:,0], y) over B*H*W into loss (1 fp32); dlogits (nullable) = d loss * loss_scale [* amp scale] / d logits
  * (zero on channels > 0).  Fixed-order reduction: same inputs, same bits.  ws: cmu_mse_ws_bytes().                           */
 int64_t cmu_mse_ws_bytes(void);
