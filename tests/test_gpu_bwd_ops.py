@@ -55,6 +55,8 @@ def test_bn_relu_backward(ops, dt, shape):
     dy = ops.new_act(B, H, W, C, dt, "cuda")
     ops.bn_bwd_apply(da, ya, mean.cuda(), invstd.cuda(), coef, dy)
     # the ReLU gate is evaluated on fp32 scale/shift: elements within rounding of 0 may flip -> tolerance on few
+    # (only because this oracle uses the unrounded float64 scale/shift: given the fp32 vectors the kernel receives, the gate is
+    # reproducible exactly -- tests/test_gpu_elem_fp64.py holds the same kernels to per-element bounds without a gate tolerance)
     check(dgamma.cpu(), gd.grad, 2e-3, "dgamma")
     check(dbeta.cpu(), bd.grad, 2e-3, "dbeta")
     check(from_act(dy), yd.grad, max(TOL[dt], 2e-3), "dy")
