@@ -191,7 +191,7 @@ __global__ __launch_bounds__(256) void conv1x1_nchw_kernel(const typename TR::el
 #pragma unroll
                 for (int e = 0; e < EPC; ++e) {
                     f[e] = fmaf(f[e], sc[kk + e], sh[kk + e]);
-                    if (kk + e >= relu_from) f[e] = fmaxf(f[e], 0.f);
+                    if (cmu_relu_on(kk + e, relu_from)) f[e] = fmaxf(f[e], 0.f);
                 }
                 a = TR::pack(f);
             }
