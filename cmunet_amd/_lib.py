@@ -64,6 +64,8 @@ _SIGS = {
     "cmu_pack_batch": (_I, [_P, _I, _L, _I, _P]),
     "cmu_version": (_I, []),
     "cmu_set_dispatch_override": (_I, [ctypes.c_char_p, _I]),
+    "cmu_dispatch_knob_name": (ctypes.c_char_p, [_I]),
+    "cmu_get_dispatch_knob": (_I, [ctypes.c_char_p, ctypes.POINTER(_I), ctypes.POINTER(_I)]),
     "cmu_mfma_sustained_rate": (_I, [_I, _I, _I, _I, _P, _P, _P, _P]),
     "cmu_probe_stream_reduce": (_I, [_P, _P, _P, _L, _I, _I, _P]),
     "cmu_dtype_size": (_I, [_I]),

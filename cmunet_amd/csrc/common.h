@@ -31,12 +31,28 @@ void cmu_set_kernel_tag(const char* tag);
 
 static inline bool cmu_aligned16(const void* p) { return (reinterpret_cast<uintptr_t>(p) & 15) == 0; }
 
-// Dispatch switches that tests A/B inside ONE process (elementwise.hip): the environment variable of the same name is read ONCE
-// (no getenv on the launch path: an environment scan per conv launch, racing with setenv from loader threads -- advisor, round 3);
-// cmu_set_dispatch_override (test entry of the C-ABI) forces a value afterwards.  Default of every switch: on.
-enum CmuSwitch { CMU_SW_CONV_NARROW = 0, CMU_SW_CONV_SLIM, CMU_SW_CONV_PERSIST_PART, CMU_SW_WGRAD_SQUARE, CMU_SW_WGRAD_WIDE_F32, CMU_SW_CONV_V5, CMU_SW_CONV_V6, CMU_SW_COUNT };
-bool cmu_switch_on(int id);
-bool cmu_switch_forced(int id);
+// Every dispatch knob of the library, X(id, kind, default, floor), for the environment variable "CMU_" #id (tools/README.md: what each one
+// does).  cmu_knob (elementwise.hip) is the only reader: it reads the variable ONCE per process (no environment scan per conv launch, racing
+// with setenv from loader threads -- advisor, round 3); cmu_set_dispatch_override (test entry of the C-ABI) forces a value afterwards.
+//   ON     on / off, default on: off iff the value starts with '0'
+//   OPTIN  on / off, default off: on iff the value starts with '1'
+//   NUM    atoi of the value when set, else the default; a value below the row's floor falls back to the default
+#define CMU_KNOBS(X)                                                                                                          \
+    X(CONV_NARROW, ON, 1, 0) X(CONV_SLIM, ON, 1, 0) X(CONV_PERSIST_PART, ON, 1, 0) X(WGRAD_SQUARE, ON, 1, 0)                      \
+    X(WGRAD_WIDE_F32, ON, 1, 0) X(CONV_V5, ON, 1, 0) X(CONV_PERSIST, ON, 1, 0) X(CONV_WRES, ON, 1, 0)                             \
+    X(CONV_BUFLOAD, ON, 1, 0) X(SPARK_GATHER, ON, 1, 0) X(CONVT_SMALL, ON, 1, 0) X(CONVT_GEMM, ON, 1, 0)                          \
+    X(WGR_VEC, ON, 1, 0) X(WGRAD_WIDE, ON, 1, 0) X(WGRAD_SWAP, ON, 1, 0) X(WGT2_NX256, ON, 1, 0)                                  \
+    X(CONV_V6, OPTIN, 0, 0)                                                                                                       \
+    X(CONV_WIDE, NUM, 1, INT32_MIN) /* 0: off, 2: every 64-channel layer goes wide */ X(CONV_PERSIST_GRID, NUM, 0, INT32_MIN)     \
+    X(GATHER_NB, NUM, 0, INT32_MIN) X(CONVT_SMALL_STEPS, NUM, 4, INT32_MIN) X(V5_MIN_K, NUM, 128, INT32_MIN)                      \
+    X(V5_MIN_K_BST, NUM, 256, INT32_MIN) X(V6_MAX_N, NUM, 128, INT32_MIN) X(V6_MAX_N_K128, NUM, 64, INT32_MIN)                    \
+    X(SKF_WGS, NUM, 768, INT32_MIN) X(WGRAD_BLOCKS1, NUM, 512, 8) X(WGRAD_BLOCKS, NUM, 256, 8)
+enum CmuKnobKind { CMU_KNOB_ON, CMU_KNOB_OPTIN, CMU_KNOB_NUM };
+#define CMU_KNOB_ENUM(id, kind, dflt, floor) CMU_KNOB_##id,
+enum CmuKnob { CMU_KNOBS(CMU_KNOB_ENUM) CMU_KNOB_COUNT };
+#undef CMU_KNOB_ENUM
+int cmu_knob(int id);           // the value in effect: the override if one is set, else the environment's, else the default
+bool cmu_knob_forced(int id);   // the override is 1
 
 // the calling thread's current HIP device (the one its launches go to)
 static inline int cmu_current_device() {

@@ -274,7 +274,7 @@ static int launch_conv_gather(IGParams p, int64_t max_rows, hipStream_t st) {
     // 256 output channels per workgroup stage the fewest bytes per MFMA, but the deep levels have few rows: level 5 of the bench
     // shape (8,192 active pixels = 32 row tiles) gives 128 workgroups at N = 1,024 and 64 at N = 512 -- half / a quarter of the chip.
     // Where the 256-channel grid does not fill the CUs, 128 channels per workgroup double it (CMU_GATHER_NB=128|256 forces a form: A/B).
-    static const int forced = []() { const char* e = getenv("CMU_GATHER_NB"); return e ? atoi(e) : 0; }();
+    const int forced = cmu_knob(CMU_KNOB_GATHER_NB);
     bool wide = p.N % 256 == 0;
     if (wide && forced == 0) wide = cmu_div_up64(max_rows, 256) * (p.N / 256) >= cmu_num_cus();
     if (forced == 128) wide = false;

@@ -471,8 +471,8 @@ static int launch_conv_gemm_s(IGParams p, hipStream_t st, const char* name) {
 // CMU_CONVT_SMALL=0 switches it off (A/B)
 template <class TR>
 static bool conv_gemm_s_eligible(const IGParams& p, bool dg) {
-    static const bool on = []() { const char* e = getenv("CMU_CONVT_SMALL"); return !(e && e[0] == '0'); }();
-    static const int max_steps = []() { const char* e = getenv("CMU_CONVT_SMALL_STEPS"); return e ? atoi(e) : 4; }();
+    const bool on = cmu_knob(CMU_KNOB_CONVT_SMALL);
+    const int max_steps = cmu_knob(CMU_KNOB_CONVT_SMALL_STEPS);
     constexpr int KSC = 128 / (int)sizeof(typename TR::elem_t);
     if (!on || sizeof(typename TR::elem_t) != 2 || p.N % 128 != 0 || p.K % KSC != 0 || p.K / KSC > max_steps) return false;
     if (dg && (p.K / 4) % KSC != 0) return false;
@@ -486,7 +486,7 @@ static bool conv_gemm_s_eligible(const IGParams& p, bool dg) {
 // CMU_CONVT_GEMM=0 keeps ConvTranspose forward / data gradient on the first kernel (A/B switch)
 template <class TR>
 static bool conv_gemm_eligible(const IGParams& p, bool dg) {
-    static const bool on = []() { const char* e = getenv("CMU_CONVT_GEMM"); return !(e && e[0] == '0'); }();
+    const bool on = cmu_knob(CMU_KNOB_CONVT_GEMM);
     constexpr int KSC = 128 / (int)sizeof(typename TR::elem_t);
     if (!on || p.N % 256 != 0 || p.K % KSC != 0) return false;
     if (dg && (p.K / 4) % KSC != 0) return false;                 // a 128-byte step stays inside one sub-pixel position

@@ -582,8 +582,7 @@ static int conv3x3_fwd_t(IGParams p, hipStream_t st) {
     p.nslices = cmu_div_up(p.K, C::KC);
     p.nslices32 = cmu_div_up(p.K, C::KC / 2);
     p.npad = cmu_conv3x3_npad(p.N);
-    static const bool bufload = []() { const char* e = getenv("CMU_CONV_BUFLOAD"); return !(e && e[0] == '0'); }();
-    p.buf_ok = bufload && ((int64_t)p.H * p.W * p.ldx + p.K) * (int64_t)sizeof(typename TR::elem_t) < 0x7fff0000ll &&
+    p.buf_ok = cmu_knob(CMU_KNOB_CONV_BUFLOAD) && ((int64_t)p.H * p.W * p.ldx + p.K) * (int64_t)sizeof(typename TR::elem_t) < 0x7fff0000ll &&
                (int64_t)p.nslices32 * 9 * p.npad * 32 < 0x7fff0000ll;
     return launch_igemm<TR, MODE_CONV3>(p, st, "cmu_conv3x3_fwd");
 }
@@ -721,7 +720,7 @@ __global__ void sparse_tile_list_kernel(const uint8_t* __restrict__ active, int 
 template <class TR>
 static int conv3x3_rows_ok_t(IGParams p) {
     constexpr int KSC = 128 / (int)sizeof(typename TR::elem_t);
-    static const bool on = []() { const char* e = getenv("CMU_SPARK_GATHER"); return !(e && e[0] == '0'); }();
+    const bool on = cmu_knob(CMU_KNOB_SPARK_GATHER);
     if (!on || p.N % 128 != 0 || p.K % KSC != 0) return 0;
     const int64_t px = (int64_t)p.B * p.H * p.W;
     if ((px * p.ldx + p.K) * (int64_t)sizeof(typename TR::elem_t) >= 0x7fff0000ll) return 0;          // 32-bit buffer offsets over the whole tensor

@@ -585,16 +585,9 @@ static int launch_igemm3_cfg(IGParams p, hipStream_t st) {
 static bool cmu_conv_persist_enabled();   // conv_igemm3p.inc
 // CMU_CONV_PERSIST_PART=0: shapes with partial tiles stay on the one-tile kernel (A/B switch: environment read once; tests flip it
 // through cmu_set_dispatch_override)
-static bool igemm3_persist_part_enabled() { return cmu_switch_on(CMU_SW_CONV_PERSIST_PART); }
+static bool igemm3_persist_part_enabled() { return cmu_knob(CMU_KNOB_CONV_PERSIST_PART); }
 // CMU_CONV_WIDE=0 keeps every layer on the first kernel (A/B switch for the benches)
-static bool cmu_conv_wide_enabled() {
-    static int v = -1;
-    if (v < 0) {
-        const char* e = getenv("CMU_CONV_WIDE");
-        v = (e && e[0] == '0') ? 0 : 1;
-    }
-    return v == 1;
-}
+static bool cmu_conv_wide_enabled() { return cmu_knob(CMU_KNOB_CONV_WIDE) != 0; }
 template <class TR>
 static bool igemm3_eligible(const IGParams& p) {
     constexpr int KC = 64 / (int)sizeof(typename TR::elem_t);
@@ -602,7 +595,7 @@ static bool igemm3_eligible(const IGParams& p) {
     // 64-channel layers: NB = 64 measures +6 % over the first kernel with 128 input channels and -5 %
     // with 64 (both ~700-850 TFLOP/s: at 512 x 512 these layers run into the per-CU fetch rate, not the matrix pipe), so
     // it takes K >= 128 by default; CMU_CONV_WIDE=2 sends every 64-channel layer to it (the tests run both)
-    static const bool nb64 = []() { const char* e = getenv("CMU_CONV_WIDE"); return e && e[0] == '2'; }();
+    const bool nb64 = cmu_knob(CMU_KNOB_CONV_WIDE) == 2;
     // (the persistent form, conv_igemm3p.inc, measures 837 vs 690 TFLOP/s on 64 -> 64 at 512 x 512: with it every
     // whole-tile 64-channel layer goes wide)
     const bool persist = cmu_conv_persist_enabled() && ((p.H % 16 == 0 && p.W % 32 == 0) || igemm3_persist_part_enabled());
@@ -621,7 +614,7 @@ static bool igemm3_eligible(const IGParams& p) {
 // CMU_CONV_NARROW=0 keeps the 128-channel blocks (A/B switch).
 static int cmu_num_cus();   // conv_igemm3p.inc
 static bool igemm3_narrow_blocks(const IGParams& p, int tw = 32) {
-    if (!cmu_switch_on(CMU_SW_CONV_NARROW) || p.N % 128 != 0) return false;   // (tests flip it through cmu_set_dispatch_override)
+    if (!cmu_knob(CMU_KNOB_CONV_NARROW) || p.N % 128 != 0) return false;   // (tests flip it through cmu_set_dispatch_override)
     const int64_t items = (int64_t)p.B * cmu_div_up(p.W, tw) * cmu_div_up(p.H, 16) * (p.N / 128);
     return 2 * items <= cmu_num_cus();
 }
@@ -632,7 +625,7 @@ static bool igemm3_narrow_blocks(const IGParams& p, int tw = 32) {
 // Measured (tools/slim_sweep.sh): 1024 -> 1024 @ 16 x 16, bs 32: f32 2.12 -> 1.10 ms, f16 0.236 -> 0.162 ms; @ 14 x 14 the same ratios.
 // Same MFMA order per accumulator -> bit-identical outputs.  CMU_CONV_SLIM=0: off (A/B switch; cmu_set_dispatch_override in tests).
 static bool igemm3_slim_tiles(const IGParams& p, int es) {
-    if (!cmu_switch_on(CMU_SW_CONV_SLIM)) return false;
+    if (!cmu_knob(CMU_KNOB_CONV_SLIM)) return false;
     const int c16 = cmu_div_up(p.W, 16);
     if (!(c16 & 1)) return false;
     if (c16 == 1) return true;

@@ -730,7 +730,7 @@ static int launch_igemm3p_cfg(IGParams p, hipStream_t st) {
     cmu_fastdiv_init((unsigned)p.tilesX, p.fd_tx);
     cmu_fastdiv_init((unsigned)p.tilesY, p.fd_ty);
     // CMU_CONV_PERSIST_GRID=n: test knob, forces n workgroups (long item lists per workgroup on small shapes)
-    static const int forced = []() { const char* e = getenv("CMU_CONV_PERSIST_GRID"); return e ? atoi(e) : 0; }();
+    const int forced = cmu_knob(CMU_KNOB_CONV_PERSIST_GRID);
     const int64_t want = forced > 0 ? forced : cmu_num_cus();
     const int64_t grid = p.total_blocks < want ? p.total_blocks : want;
     hipLaunchKernelGGL((conv_igemm3p_kernel<TR, NB, TF, BST, THB, WRES, PART>), dim3((unsigned)grid), dim3(512), P::LDS_BYTES, st, p);
@@ -740,14 +740,7 @@ static int launch_igemm3p_cfg(IGParams p, hipStream_t st) {
 }
 
 // CMU_CONV_PERSIST=0 keeps the one-tile-per-workgroup kernel (A/B switch)
-static bool cmu_conv_persist_enabled() {
-    static int v = -1;
-    if (v < 0) {
-        const char* e = getenv("CMU_CONV_PERSIST");
-        v = (e && e[0] == '0') ? 0 : 1;
-    }
-    return v == 1;
-}
+static bool cmu_conv_persist_enabled() { return cmu_knob(CMU_KNOB_CONV_PERSIST); }
 template <class TR> static bool igemm5_eligible(const IGParams& p);   // conv_igemm5.inc
 template <class TR> static int launch_igemm5(const IGParams& p, hipStream_t st);
 template <class TR> static bool igemm6_eligible(const IGParams& p);   // conv_igemm6.inc
@@ -782,8 +775,7 @@ static int launch_igemm3_any(const IGParams& p, hipStream_t st) {
     // 64 -> 64 at 16 bits (four slices, one channel block): the weight pack stays resident in LDS (IG3PCfg, WRES); CMU_CONV_WRES=0
     // keeps the streaming form (A/B switch)
     if constexpr (sizeof(typename TR::elem_t) == 2) {
-        static const bool wres_on = []() { const char* e = getenv("CMU_CONV_WRES"); return !(e && e[0] == '0'); }();
-        if (wres_on && p.N == 64 && p.K == 64)
+        if (cmu_knob(CMU_KNOB_CONV_WRES) && p.N == 64 && p.K == 64)
             return tf ? launch_igemm3p_cfg<TR, 64, true, false, 1, true>(p, st)
                       : (bst ? launch_igemm3p_cfg<TR, 64, false, true, 1, true>(p, st) : launch_igemm3p_cfg<TR, 64, false, false, 1, true>(p, st));
     }

@@ -780,7 +780,7 @@ static int launch_igemm5_cfg(IGParams p, hipStream_t st) {
     cmu_fastdiv_init((unsigned)p.nblk, p.fd_nblk);
     cmu_fastdiv_init((unsigned)p.tilesX, p.fd_tx);
     cmu_fastdiv_init((unsigned)p.tilesY, p.fd_ty);
-    static const int forced = []() { const char* e = getenv("CMU_CONV_PERSIST_GRID"); return e ? atoi(e) : 0; }();
+    const int forced = cmu_knob(CMU_KNOB_CONV_PERSIST_GRID);
     const int64_t want = forced > 0 ? forced : cmu_num_cus();
     const int64_t grid = p.total_blocks < want ? p.total_blocks : want;
     hipLaunchKernelGGL((conv_igemm5_kernel<TR, TF, BST>), dim3((unsigned)grid), dim3(512), BST ? C::LDS_BYTES_BST : C::LDS_BYTES, st, p);
@@ -793,14 +793,13 @@ static int launch_igemm5_cfg(IGParams p, hipStream_t st) {
 template <class TR>
 static bool igemm5_eligible(const IGParams& p) {
     if constexpr (sizeof(typename TR::elem_t) != 2) return false;
-    if (!cmu_switch_on(CMU_SW_CONV_V5)) return false;
+    if (!cmu_knob(CMU_KNOB_CONV_V5)) return false;
     if (p.tile_list != nullptr) return false;
     if (p.in_scale != nullptr && p.bstats != nullptr) return false;
     if (p.N % 128 != 0 || p.K % 64 != 0) return false;
     // measured against conv_igemm3p (tools/v5_check.py, f16, bs 32, same box): K = 64 (two positions per item) loses 5 %; the data-gradient
     // form with its BatchNorm-backward epilogue loses 4-5 % at K = 128 and gains from K = 256 up
-    static const int min_k = []() { const char* e = getenv("CMU_V5_MIN_K"); return e ? atoi(e) : 128; }();          // (A/B knobs, read once)
-    static const int min_k_bst = []() { const char* e = getenv("CMU_V5_MIN_K_BST"); return e ? atoi(e) : 256; }();
+    const int min_k = cmu_knob(CMU_KNOB_V5_MIN_K), min_k_bst = cmu_knob(CMU_KNOB_V5_MIN_K_BST);          // (A/B knobs)
     if (p.K < min_k || (p.bstats != nullptr && p.K < min_k_bst)) return false;
     if (p.H % 16 != 0 || p.W % 32 != 0) return false;
     if ((int64_t)p.B * (p.H / 16) * (p.W / 32) * (p.N / 128) >= (1ll << 30)) return false;

@@ -497,7 +497,7 @@ static int launch_igemm6_cfg(IGParams p, hipStream_t st) {
     cmu_fastdiv_init((unsigned)p.nblk, p.fd_nblk);
     cmu_fastdiv_init((unsigned)p.tilesX, p.fd_tx);
     cmu_fastdiv_init((unsigned)p.tilesY, p.fd_ty);
-    static const int forced = []() { const char* e = getenv("CMU_CONV_PERSIST_GRID"); return e ? atoi(e) : 0; }();
+    const int forced = cmu_knob(CMU_KNOB_CONV_PERSIST_GRID);
     const int64_t want = forced > 0 ? forced : 2 * cmu_num_cus();
     const int64_t grid = p.total_blocks < want ? p.total_blocks : want;
     hipLaunchKernelGGL((conv_igemm6_kernel<TR, TF>), dim3((unsigned)grid), dim3(256), C::LDS_BYTES, st, p);
@@ -515,18 +515,14 @@ static int launch_igemm6_cfg(IGParams p, hipStream_t st) {
 template <class TR>
 static bool igemm6_eligible(const IGParams& p) {
     if constexpr (sizeof(typename TR::elem_t) != 2) return false;
-    if (!cmu_switch_on(CMU_SW_CONV_V6)) return false;
     if (p.tile_list != nullptr || p.bstats != nullptr) return false;
     if (p.N % 64 != 0 || p.K % 64 != 0 || p.K > IG6Cfg::MAX_K) return false;      // whole pairs of 64-byte slices
     if (p.H % 16 != 0 || p.W % 32 != 0) return false;
     const int64_t items = (int64_t)p.B * (p.H / 16) * (p.W / 32) * (p.N / 64);
     if (items >= (1ll << 30)) return false;
-    if (cmu_switch_forced(CMU_SW_CONV_V6)) return true;     // tests (cmu_set_dispatch_override(..., 1)): every shape the kernel can serve
-    static const bool env_on = []() { const char* e = getenv("CMU_CONV_V6"); return e && e[0] == '1'; }();
-    if (!env_on) return false;                              // opt-in (see above)
-    static const int max_n = []() { const char* e = getenv("CMU_V6_MAX_N"); return e ? atoi(e) : 128; }();
-    static const int max_n_k128 = []() { const char* e = getenv("CMU_V6_MAX_N_K128"); return e ? atoi(e) : 64; }();
-    if (p.N > max_n || (p.K > 64 && p.N > max_n_k128)) return false;
+    if (cmu_knob_forced(CMU_KNOB_CONV_V6)) return true;     // tests (cmu_set_dispatch_override(..., 1)): every shape the kernel can serve
+    if (!cmu_knob(CMU_KNOB_CONV_V6)) return false;          // opt-in (see above): the knob's default is off
+    if (p.N > cmu_knob(CMU_KNOB_V6_MAX_N) || (p.K > 64 && p.N > cmu_knob(CMU_KNOB_V6_MAX_N_K128))) return false;
     return items >= 4 * (int64_t)cmu_num_cus();     // small launches stay on the one-round forms
 }
 template <class TR>

@@ -428,8 +428,7 @@ __global__ __launch_bounds__(256) void wgrad_reduce4_kernel(const float* __restr
 }
 // CMU_WGR_VEC=0 keeps the scalar reduction (A/B switch)
 static void launch_wgrad_reduce(const float* ws, int splitk, int T, int CApad, int CBpad, int CA, int CB, float* dW, int mode, hipStream_t st) {
-    static const bool vec_on = []() { const char* e = getenv("CMU_WGR_VEC"); return !(e && e[0] == '0'); }();
-    const bool vec = vec_on && (reinterpret_cast<uintptr_t>(ws) & 15) == 0 && (mode == 2 ? CA % 4 == 0 : (CB % 4 == 0 && CBpad % 4 == 0));
+    const bool vec = cmu_knob(CMU_KNOB_WGR_VEC) && (reinterpret_cast<uintptr_t>(ws) & 15) == 0 && (mode == 2 ? CA % 4 == 0 : (CB % 4 == 0 && CBpad % 4 == 0));
     const int64_t total = (int64_t)T * CA * CB / (vec ? 4 : 1);
     const int grid = (int)(cmu_div_up64(total, 64) < CMU_WGR_CAP ? cmu_div_up64(total, 64) : CMU_WGR_CAP);
     if (vec) hipLaunchKernelGGL(wgrad_reduce4_kernel, dim3(grid), dim3(256), 0, st, ws, splitk, T, CApad, CBpad, CA, CB, dW, mode);
@@ -512,14 +511,8 @@ static int wg_splitk(int nbase, int ntiles, int mult, int target = 512) {
 // the wide kernels hold one workgroup per CU (LDS): 256 workgroups are exactly one round over the chip, and every
 // workgroup writes its whole accumulator tile to the split-K slab -- half the workgroups is half the slab traffic of
 // the reduction (1.1 ms per bench step at 512).  CMU_WGRAD_BLOCKS overrides (A/B).
-static int cmu_wg_first_target() {
-    static const int v = []() { const char* e = getenv("CMU_WGRAD_BLOCKS1"); const int n = e ? atoi(e) : 512; return n >= 8 ? n : 512; }();
-    return v;
-}
-static int cmu_wg_wide_target() {
-    static const int v = []() { const char* e = getenv("CMU_WGRAD_BLOCKS"); const int n = e ? atoi(e) : 256; return n >= 8 ? n : 256; }();
-    return v;
-}
+static int cmu_wg_first_target() { return cmu_knob(CMU_KNOB_WGRAD_BLOCKS1); }
+static int cmu_wg_wide_target() { return cmu_knob(CMU_KNOB_WGRAD_BLOCKS); }
 static void wg_geometry(int B, int H, int W, int CA, int CB, int dt, int mult, WGParams& p) {
     const int CW = 128 / cmu_dtype_size(dt);
     p.tilesX = cmu_div_up(W, 16);
@@ -536,15 +529,12 @@ constexpr int CSUM_BLOCKS = 256;
 // wide-tile kernel (conv_wgrad2.inc): 16-bit dtypes, Cout in whole 128-blocks, Cin in whole 64-blocks.  CMU_WGRAD_WIDE=0 keeps
 // every layer on the first kernel (A/B switch for the benches).
 static bool wg2_shape_ok(int CA, int CB, int dt) {
-    static const bool on = []() { const char* e = getenv("CMU_WGRAD_WIDE"); return !(e && e[0] == '0'); }();
-    return on && cmu_dtype_size(dt) == 2 && CA % 128 == 0 && CB % 64 == 0;
+    return cmu_knob(CMU_KNOB_WGRAD_WIDE) && cmu_dtype_size(dt) == 2 && CA % 128 == 0 && CB % 64 == 0;
 }
 // swapped roles (conv_wgrad2.inc, SWAP): Cout = 64 with Cin in whole 128-blocks.  CMU_WGRAD_SWAP=0 keeps those layers on the
 // first kernel (A/B switch)
 static bool wg2_swap_ok(int CA, int CB, int dt) {
-    static const bool on = []() { const char* e = getenv("CMU_WGRAD_SWAP"); return !(e && e[0] == '0'); }();
-    static const bool wide = []() { const char* e = getenv("CMU_WGRAD_WIDE"); return !(e && e[0] == '0'); }();
-    return on && wide && cmu_dtype_size(dt) == 2 && CA == 64 && CB % 128 == 0;
+    return cmu_knob(CMU_KNOB_WGRAD_SWAP) && cmu_knob(CMU_KNOB_WGRAD_WIDE) && cmu_dtype_size(dt) == 2 && CA == 64 && CB % 128 == 0;
 }
 static void wg2_geometry(int B, int H, int W, int CA, int CB, WGParams& p, bool swap = false) {
     p.tilesX = cmu_div_up(W, 16);
@@ -557,13 +547,11 @@ static void wg2_geometry(int B, int H, int W, int CA, int CB, WGParams& p, bool 
     p.splitk = wg_splitk(p.nAB * p.nBB, p.ntiles, 1, cmu_wg_wide_target());
 }
 static bool wgT2_shape_ok(int CA, int CB, int dt) {
-    static const bool on = []() { const char* e = getenv("CMU_WGRAD_WIDE"); return !(e && e[0] == '0'); }();
-    return on && cmu_dtype_size(dt) == 2 && CA % 64 == 0 && CB % 128 == 0;
+    return cmu_knob(CMU_KNOB_WGRAD_WIDE) && cmu_dtype_size(dt) == 2 && CA % 64 == 0 && CB % 128 == 0;
 }
 // 256 X channels per workgroup (conv_wgrad2.inc, NXI = 4) where Cin allows: the deeper decoder levels (CMU_WGT2_NX256=0: A/B)
 static bool wgT2_wide_x(int CB) {
-    static const bool on = []() { const char* e = getenv("CMU_WGT2_NX256"); return !(e && e[0] == '0'); }();
-    return on && CB % 256 == 0;
+    return cmu_knob(CMU_KNOB_WGT2_NX256) && CB % 256 == 0;
 }
 static void wgT2_geometry(int B, int H, int W, int CA, int CB, WGParams& p) {
     p.tilesX = cmu_div_up(W, 16);
@@ -639,8 +627,7 @@ static int wgrad3_wide_t(WGParams p, float* dW, hipStream_t st) {
 // 64 n x 64 c form for the 16-bit dtypes (conv_wgrad2s.inc): whole 64-blocks on both sides where neither form above applies (the
 // 64 -> 64 layers).  CMU_WGRAD_SQUARE=0 keeps them on the first kernel (A/B switch: environment read once, cmu_set_dispatch_override in tests).
 static bool wg2s_shape_ok(int CA, int CB, int dt) {
-    static const bool wide = []() { const char* e = getenv("CMU_WGRAD_WIDE"); return !(e && e[0] == '0'); }();
-    return wide && cmu_switch_on(CMU_SW_WGRAD_SQUARE) && cmu_dtype_size(dt) == 2 && CA % 64 == 0 && CB % 64 == 0 && !wg2_shape_ok(CA, CB, dt) &&
+    return cmu_knob(CMU_KNOB_WGRAD_WIDE) && cmu_knob(CMU_KNOB_WGRAD_SQUARE) && cmu_dtype_size(dt) == 2 && CA % 64 == 0 && CB % 64 == 0 && !wg2_shape_ok(CA, CB, dt) &&
            !wg2_swap_ok(CA, CB, dt);
 }
 static void wg2s_geometry(int B, int H, int W, int CA, int CB, WGParams& p) {
@@ -683,8 +670,7 @@ static int wgrad3_square_t(WGParams p, float* dW, hipStream_t st) {
 // fp32 wide kernel (conv_wgrad2f.inc): Cout and Cin in whole 64-blocks (128 n x 64 c blocks when Cout allows, else 64 x 64 with two
 // k-parts).  CMU_WGRAD_WIDE_F32=0 keeps fp32 on the first kernel (A/B switch: environment read once, cmu_set_dispatch_override in tests).
 static bool wg2f_shape_ok(int CA, int CB, int dt) {
-    static const bool wide = []() { const char* e = getenv("CMU_WGRAD_WIDE"); return !(e && e[0] == '0'); }();
-    return wide && cmu_switch_on(CMU_SW_WGRAD_WIDE_F32) && dt == CMU_F32 && CA % 64 == 0 && CB % 64 == 0;
+    return cmu_knob(CMU_KNOB_WGRAD_WIDE) && cmu_knob(CMU_KNOB_WGRAD_WIDE_F32) && dt == CMU_F32 && CA % 64 == 0 && CB % 64 == 0;
 }
 static void wg2f_geometry(int B, int H, int W, int CA, int CB, WGParams& p) {
     p.tilesX = cmu_div_up(W, 16);

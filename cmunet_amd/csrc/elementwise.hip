@@ -25,36 +25,55 @@ void cmu_set_kernel_tag(const char* tag) { g_kernel_tag = tag; }
 extern "C" const char* cmu_last_kernel(void) { return g_kernel_tag; }
 extern "C" int cmu_version(void) { return 100; }
 
-// ---- dispatch switches (common.h: CmuSwitch) -----------------------------------------------------------------------------------
-static const char* const g_switch_names[CMU_SW_COUNT] = {"CMU_CONV_NARROW", "CMU_CONV_SLIM", "CMU_CONV_PERSIST_PART", "CMU_WGRAD_SQUARE",
-                                                         "CMU_WGRAD_WIDE_F32", "CMU_CONV_V5", "CMU_CONV_V6"};
-static int g_switch_env[CMU_SW_COUNT] = {-1, -1, -1, -1, -1, -1, -1};        // -1: environment not read yet; 0 / 1 afterwards
-static int g_switch_override[CMU_SW_COUNT] = {-1, -1, -1, -1, -1, -1, -1};   // -1: no override
-bool cmu_switch_on(int id) {
-    const int ov = __atomic_load_n(&g_switch_override[id], __ATOMIC_RELAXED);
-    if (ov >= 0) return ov != 0;
-    int v = __atomic_load_n(&g_switch_env[id], __ATOMIC_RELAXED);
-    if (v < 0) {
-        const char* e = getenv(g_switch_names[id]);
-        v = (e && e[0] == '0') ? 0 : 1;
-        __atomic_store_n(&g_switch_env[id], v, __ATOMIC_RELAXED);
+// ---- dispatch knobs (common.h: CMU_KNOBS) ---------------------------------------------------------------------------------------
+#define CMU_KNOB_UNREAD INT32_MIN
+struct CmuKnobRow {
+    const char* name;
+    int kind, dflt, floor;
+    int env = CMU_KNOB_UNREAD, ovr = -1;   // the environment's value once it has been read; the override (-1: none)
+};
+#define CMU_KNOB_ROW(id, kind, dflt, floor) {"CMU_" #id, CMU_KNOB_##kind, dflt, floor},
+static CmuKnobRow g_knobs[CMU_KNOB_COUNT] = {CMU_KNOBS(CMU_KNOB_ROW)};
+int cmu_knob(int id) {
+    CmuKnobRow& k = g_knobs[id];
+    const int ov = __atomic_load_n(&k.ovr, __ATOMIC_RELAXED);
+    if (ov >= 0) return ov;
+    int v = __atomic_load_n(&k.env, __ATOMIC_RELAXED);
+    if (v == CMU_KNOB_UNREAD) {
+        const char* e = getenv(k.name);
+        if (k.kind == CMU_KNOB_ON) v = (e && e[0] == '0') ? 0 : 1;
+        else if (k.kind == CMU_KNOB_OPTIN) v = (e && e[0] == '1') ? 1 : 0;
+        else v = e ? atoi(e) : k.dflt;
+        if (v < k.floor) v = k.dflt;
+        __atomic_store_n(&k.env, v, __ATOMIC_RELAXED);
     }
-    return v != 0;
+    return v;
 }
-// 1 while a test forces the switch ON through cmu_set_dispatch_override (conv_igemm6: a forced switch also lifts the launch-size gates)
-bool cmu_switch_forced(int id) { return __atomic_load_n(&g_switch_override[id], __ATOMIC_RELAXED) == 1; }
+// true while a test forces the knob to 1 through cmu_set_dispatch_override (conv_igemm6: a forced switch also lifts the launch-size gates)
+bool cmu_knob_forced(int id) { return __atomic_load_n(&g_knobs[id].ovr, __ATOMIC_RELAXED) == 1; }
+static int cmu_knob_find(const char* name) {
+    for (int i = 0; name != nullptr && i < CMU_KNOB_COUNT; ++i)
+        if (strcmp(name, g_knobs[i].name) == 0) return i;
+    return -1;
+}
 #include <mutex>
-static std::mutex g_switch_mutex;   // (test hook: concurrent setters are serialised; readers on the launch path take relaxed atomic loads)
+static std::mutex g_knob_mutex;   // (test hook: concurrent setters are serialised; readers on the launch path take relaxed atomic loads)
 extern "C" int cmu_set_dispatch_override(const char* name, int value) {
-    CMU_CHECK_ARG(name != nullptr && value >= -1 && value <= 1, "cmu_set_dispatch_override: value must be -1 (environment), 0 or 1");
-    std::lock_guard<std::mutex> lock(g_switch_mutex);
-    for (int i = 0; i < CMU_SW_COUNT; ++i)
-        if (strcmp(name, g_switch_names[i]) == 0) {
-            __atomic_store_n(&g_switch_override[i], value, __ATOMIC_RELAXED);
-            return CMU_OK;
-        }
-    cmu_set_error("cmu_set_dispatch_override: unknown switch '%s'", name);
-    return CMU_ERR_ARG;
+    const int i = cmu_knob_find(name);
+    CMU_CHECK_ARG(i >= 0, "cmu_set_dispatch_override: unknown knob '%s'", name ? name : "(null)");
+    CMU_CHECK_ARG(value >= -1 && (value <= 1 || g_knobs[i].kind == CMU_KNOB_NUM),
+                  "cmu_set_dispatch_override: %s takes -1 (environment)%s", name, g_knobs[i].kind == CMU_KNOB_NUM ? " or a number >= 0" : ", 0 or 1");
+    std::lock_guard<std::mutex> lock(g_knob_mutex);
+    __atomic_store_n(&g_knobs[i].ovr, value >= 0 && value < g_knobs[i].floor ? g_knobs[i].dflt : value, __ATOMIC_RELAXED);
+    return CMU_OK;
+}
+extern "C" const char* cmu_dispatch_knob_name(int index) { return index >= 0 && index < CMU_KNOB_COUNT ? g_knobs[index].name : nullptr; }
+extern "C" int cmu_get_dispatch_knob(const char* name, int* value, int* dflt) {
+    const int i = cmu_knob_find(name);
+    CMU_CHECK_ARG(i >= 0 && value != nullptr && dflt != nullptr, "cmu_get_dispatch_knob: unknown knob or null pointer");
+    *value = cmu_knob(i);
+    *dflt = g_knobs[i].dflt;
+    return CMU_OK;
 }
 extern "C" int cmu_dtype_size(int dt) { return dt == CMU_F32 ? 4 : (dt == CMU_F16 || dt == CMU_BF16) ? 2 : 0; }
 

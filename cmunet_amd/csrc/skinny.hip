@@ -118,7 +118,7 @@ static int skf_splits(int N, int64_t K, int64_t* kchunk) {
     const int nblk = cmu_div_up(N, 128);
     // three workgroups fit a CU (LDS): one round of 768 measured best at both projector shapes (512: 0.49 / 0.083 ms, 768: 0.413 /
     // 0.081, 1,024: 0.436 / 0.095, 1,536: 0.434 / 0.098 at K = 262,144 / 50,176); CMU_SKF_WGS overrides (A/B)
-    static const int target = []() { const char* e = getenv("CMU_SKF_WGS"); return e ? atoi(e) : 768; }();
+    const int target = cmu_knob(CMU_KNOB_SKF_WGS);
     int splits = (int)cmu_div_up64(target, nblk);
     int64_t kc = cmu_div_up64(K, splits);
     kc = cmu_div_up64(kc, SKF_KC) * SKF_KC;

@@ -54,8 +54,10 @@ def mfma_sustained_rate(dt="f16", pattern=0, lds_fed=False, iters=60000, device=
 
 
 class dispatch_override:
-    """``with ops.dispatch_override("CMU_CONV_NARROW", 0): ...`` -- force one of the library's A/B dispatch switches for the
-    launches inside the block (cmu_set_dispatch_override; the switches' environment variables are read once, not per launch)."""
+    """``with ops.dispatch_override("CMU_CONV_NARROW", 0): ...`` -- force one of the library's dispatch knobs (any row of the table in
+    tools/README.md: 0 / 1 for the on / off and opt-in knobs, a number >= 0 for the others) for the launches inside the block
+    (cmu_set_dispatch_override; the knobs' environment variables are read once, not per launch).  CMU_CONV_NARROW, CMU_CONV_SLIM,
+    CMU_CONV_PERSIST_PART, CMU_WGRAD_SQUARE and CMU_WGRAD_WIDE_F32 give the same bits either way; every other knob is equal to rounding."""
 
     def __init__(self, name, value):
         self.name, self.value = name.encode(), int(value)

@@ -44,14 +44,20 @@ const char* cmu_last_error(void);
 const char* cmu_last_kernel(void);
 int cmu_version(void);
 /* TEST HOOK -- the one piece of process-global mutable state in this library (every other entry is re-entrant and keeps no state
- * between calls: SURVEY section 8b).  Forces one of the dispatch switches that A/B two kernel forms -- "CMU_CONV_NARROW", "CMU_CONV_SLIM",
- * "CMU_CONV_PERSIST_PART", "CMU_WGRAD_SQUARE", "CMU_WGRAD_WIDE_F32" (bit-identical results either way), "CMU_CONV_V5" (the 16x16x32 conv
- * kernel of round 5 against the 32x32x16 family: equal to rounding) -- to 0 / 1, or back to the environment variable of the same name
- * (value -1; the environment is read once, never on the launch path).  The override applies to EVERY thread of the process from the
- * moment it is set: set it while no other thread is launching (the tests are single-threaded); stores and loads of the switch are atomic,
+ * between calls: SURVEY section 8b).  Forces one of the library's dispatch knobs (every environment variable it reads: cmu_dispatch_knob_name
+ * lists them, tools/README.md says what each does) or hands it back to the environment variable of the same name (value -1; the environment
+ * is read once, never on the launch path).  On / off and opt-in knobs take 0 / 1, number knobs any value >= 0.  Documented as bit-identical
+ * either way: "CMU_CONV_NARROW", "CMU_CONV_SLIM", "CMU_CONV_PERSIST_PART", "CMU_WGRAD_SQUARE", "CMU_WGRAD_WIDE_F32"; every other knob
+ * ("CMU_CONV_V5", the 16x16x32 conv kernel against the 32x32x16 family, "CMU_CONV_V6", "CMU_CONV_WIDE", "CMU_CONV_PERSIST", ...) changes the
+ * MFMA shape, the summation order or the split and is equal to rounding only.  The override applies to EVERY thread of the process from the
+ * moment it is set: set it while no other thread is launching (the tests are single-threaded); stores and loads of the knob are atomic,
  * calls are serialised by a mutex, a launch in flight on another thread may see either value.  Product code never calls it.
- * Unknown name: CMU_ERR_ARG. */
+ * Unknown name, or a value outside the knob's range: CMU_ERR_ARG. */
 int cmu_set_dispatch_override(const char* name, int value);
+/* host-only views of the knob table (no GPU call): the name of row `index` (NULL past the end); the value in effect (override, else
+ * environment, else default) and the default of one knob (unknown name: CMU_ERR_ARG) */
+const char* cmu_dispatch_knob_name(int index);
+int cmu_get_dispatch_knob(const char* name, int* value, int* dflt);
 /* element size in bytes of a cmu_dtype */
 int cmu_dtype_size(int dt);
 

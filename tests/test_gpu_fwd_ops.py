@@ -445,6 +445,44 @@ torch.save(res, sys.argv[1])
             assert torch.equal(outs[0][shape][k].view(torch.uint8), outs[1][shape][k].view(torch.uint8)), (shape, k)
 
 
+def test_dispatch_override_reaches_the_knobs_only_the_environment_reached(ops):
+    """cmu_set_dispatch_override forces EVERY row of the library's knob table, not only the seven switches it knew before: CMU_CONV_PERSIST and
+    CMU_CONV_WIDE were private lazy statics that only the environment of a fresh process could set.  One small layer (f16, 2 x 32 x 64,
+    64 -> 64: whole 16 x 32 tiles, K below CMU_V5_MIN_K) launched by default (persistent wide kernel), with CMU_CONV_WIDE forced to 0 (first
+    kernel) and with CMU_CONV_PERSIST forced to 0: cmu_last_kernel names the kernel each launch ran on, the default is back behind every
+    block, and every output meets this file's f16 bar against float64.
+    CMU_CONV_PERSIST=0 ALONE leaves this layer on the FIRST kernel, not on conv_igemm3_kernel: igemm3_eligible sends a 64-channel layer with
+    K < 128 to the wide kernels only for the persistent form or under CMU_CONV_WIDE=2 (conv_igemm3.inc; the environment gives the same
+    answer on the library before the table).  Both are asserted: the tag PERSIST=0 alone gives, and conv_igemm3_kernel for PERSIST=0 under
+    CMU_CONV_WIDE=2, the setting test_conv3x3_persistent_kernel_is_bit_identical_to_one_tile pairs it with."""
+    from cmunet_amd import _lib
+    dt, (B, H, W, Cin, Cout) = "f16", (2, 32, 64, 64, 64)
+    g = torch.Generator().manual_seed(31)
+    x = q(torch.randn(B, Cin, H, W, generator=g), dt, ops)
+    w = q(torch.randn(Cout, Cin, 3, 3, generator=g) / (Cin * 9) ** 0.5, dt, ops)
+    ref = F.conv2d(x.double(), w.double(), padding=1)
+    xa, wp = to_act(x, dt, ops), ops.pack_conv3x3(w.cuda(), dt)
+
+    def launch(what):
+        ya = ops.new_act(B, H, W, Cout, dt, "cuda")
+        ops.conv3x3_fwd(xa, wp, ya, ops.new_stats(B, H, W, Cout, "cuda"))
+        tag = _lib.lib().cmu_last_kernel().decode()
+        torch.cuda.synchronize()
+        check(from_act(ya), ref, TOL[dt], f"conv3x3 y ({what}: {tag})")
+        return tag
+
+    default = launch("default")
+    assert default == "conv_igemm3p_kernel"
+    with ops.dispatch_override("CMU_CONV_PERSIST", 0):
+        assert launch("CMU_CONV_PERSIST=0") == "conv_igemm_kernel"
+        with ops.dispatch_override("CMU_CONV_WIDE", 2):
+            assert launch("CMU_CONV_PERSIST=0, CMU_CONV_WIDE=2") == "conv_igemm3_kernel"
+    assert launch("default again") == default
+    with ops.dispatch_override("CMU_CONV_WIDE", 0):
+        assert launch("CMU_CONV_WIDE=0") == "conv_igemm_kernel"
+    assert launch("default again") == default
+
+
 @pytest.mark.parametrize("dt", DTS)
 @pytest.mark.parametrize("hw", [(32, 64), (16, 16), (28, 28)])
 def test_conv3x3_narrow_channel_blocks_equal_the_wide_ones(ops, dt, hw):
