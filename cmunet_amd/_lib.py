@@ -110,6 +110,9 @@ _SIGS = {
     "cmu_masked_mse_fwd_bwd": (_I, [_P, _I, _I, _P, _P, _P, _P, _F, _P, _I, _I, _I, _P, _P]),
     "cmu_softmax_ce_dice_ws_bytes": (_L, [_I, _I, _I]),
     "cmu_softmax_ce_dice_fwd_bwd": (_I, [_P, _P, _P, _P, _F, _I, _I, _I, _P, _P]),
+    "cmu_seg_stats_ws_bytes": (_L, [_I]),
+    "cmu_seg_stats_fwd": (_I, [_P, _P, _I, _P, _F, _P, _I, _I, _I, _I, _P, _P]),
+    "cmu_seg_stats_bwd": (_I, [_P, _P, _I, _P, _P, _P, _P, _P, _I, _I, _I, _I, _P]),
     "cmu_infonce_inbatch_fwd_bwd": (_I, [_P, _P, _P, _P, _I, _I, _I, _I, _F, _F, _P]),
     "cmu_moco_ws_bytes": (_L, [_I, _I, _I]),
     "cmu_moco_infonce_enqueue": (_I, [_P, _P, _P, _I, _P, _P, _P, _P, _P, _I, _I, _I, _F, _P, _P]),

@@ -301,6 +301,246 @@ extern "C" int cmu_softmax_ce_dice_fwd_bwd(const float* logits, const double* y1
 }
 
 // ---------------------------------------------------------------------------------------------
+// softmax CE (probability targets, optional class weights) + per-class soft and thresholded Dice / IoU counters for 2..8 classes,
+// and the backward of the CE and of the SOFT counters (metrics.py:135-198 with any threshold / ignore_channels / beta / eps: the
+// scores are a few flops on these K-vectors, cmunet_amd/metrics.py).  The class count is compiled in as KT in {2, 4, 8} (classes
+// >= K masked, as the head kernels do); a lane takes V consecutive pixels of every plane (V = 4: 16-byte loads; V = 2 at KT = 8:
+// 8-byte logits / 16-byte fp64 target loads) when H*W % V == 0 and the pointers are 16-byte aligned, one pixel otherwise -- decided
+// for the whole tensor, no scalar tail behind a vector body.  HBM-bound: 4K + 8K (fp64 targets) bytes in per pixel, 4K more out backward.
+// ws: [1 + 5K columns][CE_MAX_BLOCKS] doubles, column-major so that the finalisation reads rows of blocks coalesced.
+// table: [ce | tp_soft[K] | spr_soft[K] | tp_hard[K] | spr_hard[K] | sgt[K]] doubles.
+// ---------------------------------------------------------------------------------------------
+constexpr int SEG_MAX_K = 8;
+template <typename T, int V>
+struct alignas(sizeof(T) * V < 16 ? sizeof(T) * V : 16) SegVec {
+    T v[V];
+};
+// (image, first pixel) of pixel group g; ``small``: fewer than 2^31 groups (a 64-bit division is ~10x the instructions)
+__device__ static inline int64_t seg_group_base(int64_t g, int64_t gpi, bool small, int K, int64_t HW, int V) {
+    int64_t b, r;
+    if (small) {
+        const unsigned gu = (unsigned)g, bu = gu / (unsigned)gpi;
+        b = bu;
+        r = gu - bu * (unsigned)gpi;
+    } else {
+        b = g / gpi;
+        r = g - b * gpi;
+    }
+    return b * K * HW + r * V;
+}
+// softmax of one pixel in fp32: p[c] = e^(l[c] - max) / sum, lse = max + log(sum); classes >= K are left alone
+template <int KT>
+__device__ static inline void seg_softmax(const float (&l)[KT], int K, float (&p)[KT], float& lse) {
+    float m = l[0];
+#pragma unroll
+    for (int c = 1; c < KT; ++c)
+        if (c < K) m = fmaxf(m, l[c]);
+    float se = 0.f;
+#pragma unroll
+    for (int c = 0; c < KT; ++c)
+        if (c < K) {
+            // e^(l - m) with the rounding d of the fp32 difference given back (e^(x + d) = e^x (1 + d)): a class far below the
+            // maximum would otherwise carry |l - m| roundoffs in its probability, and through sum_c p_c G_c into every gradient
+            const float x = l[c] - m;
+            const float d = (float)(((double)l[c] - (double)m) - (double)x);
+            const float e = expf(x);
+            p[c] = fmaf(e, d, e);
+            se += p[c];
+        }
+    lse = m + logf(se);
+#pragma unroll
+    for (int c = 0; c < KT; ++c)
+        if (c < K) p[c] = p[c] / se;
+}
+
+template <int KT, int V, typename TY>
+__global__ __launch_bounds__(256) void seg_stats_kernel(const float* __restrict__ logits, const TY* __restrict__ y,
+                                                       const float* __restrict__ class_w, float thr, double* __restrict__ ws, int K,
+                                                       int64_t HW, int64_t ngroups) {
+    __shared__ double red[4];
+    double ce = 0.0, tps[KT], sps[KT], tph[KT], sph[KT], sgt[KT];
+    float wc[KT];
+#pragma unroll
+    for (int c = 0; c < KT; ++c) {
+        tps[c] = sps[c] = tph[c] = sph[c] = sgt[c] = 0.0;
+        wc[c] = (class_w && c < K) ? class_w[c] : 1.f;
+    }
+    const int64_t gpi = HW / V;
+    const bool small = ngroups < (int64_t(1) << 31);
+    for (int64_t g = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; g < ngroups; g += (int64_t)gridDim.x * blockDim.x) {
+        const int64_t base = seg_group_base(g, gpi, small, K, HW, V);
+        SegVec<float, V> lv[KT];
+        SegVec<TY, V> yv[KT];
+#pragma unroll
+        for (int c = 0; c < KT; ++c)
+            if (c < K) {
+                lv[c] = *reinterpret_cast<const SegVec<float, V>*>(logits + base + c * HW);
+                yv[c] = *reinterpret_cast<const SegVec<TY, V>*>(y + base + c * HW);
+            }
+#pragma unroll
+        for (int v = 0; v < V; ++v) {
+            float l[KT], p[KT], lse;
+#pragma unroll
+            for (int c = 0; c < KT; ++c) l[c] = c < K ? lv[c].v[v] : 0.f;
+            seg_softmax<KT>(l, K, p, lse);
+#pragma unroll
+            for (int c = 0; c < KT; ++c)
+                if (c < K) {
+                    const double yc = (double)yv[c].v[v], pc = (double)p[c];
+                    const double hard = p[c] > thr ? 1.0 : 0.0;
+                    ce -= (double)wc[c] * yc * (double)(l[c] - lse);
+                    tps[c] += yc * pc;
+                    sps[c] += pc;
+                    tph[c] += yc * hard;
+                    sph[c] += hard;
+                    sgt[c] += yc;
+                }
+        }
+    }
+    ce = block_sum_d(ce, red);
+    if (threadIdx.x == 0) ws[blockIdx.x] = ce;
+#pragma unroll
+    for (int c = 0; c < KT; ++c)
+        if (c < K) {
+            const double a0 = block_sum_d(tps[c], red), a1 = block_sum_d(sps[c], red), a2 = block_sum_d(tph[c], red),
+                         a3 = block_sum_d(sph[c], red), a4 = block_sum_d(sgt[c], red);
+            if (threadIdx.x == 0) {
+                ws[(int64_t)(1 + 0 * K + c) * CE_MAX_BLOCKS + blockIdx.x] = a0;
+                ws[(int64_t)(1 + 1 * K + c) * CE_MAX_BLOCKS + blockIdx.x] = a1;
+                ws[(int64_t)(1 + 2 * K + c) * CE_MAX_BLOCKS + blockIdx.x] = a2;
+                ws[(int64_t)(1 + 3 * K + c) * CE_MAX_BLOCKS + blockIdx.x] = a3;
+                ws[(int64_t)(1 + 4 * K + c) * CE_MAX_BLOCKS + blockIdx.x] = a4;
+            }
+        }
+}
+// one wave per column, fixed order (lane l takes blocks l, l + 64, ...; then the wave's butterfly), as ce_dice_final_kernel
+__global__ __launch_bounds__(64) void seg_stats_final_kernel(const double* __restrict__ ws, int nblocks, double npix, double* __restrict__ table) {
+    const double* col = ws + (int64_t)blockIdx.x * CE_MAX_BLOCKS;
+    double s = 0.0;
+    for (int b = threadIdx.x; b < nblocks; b += 64) s += col[b];
+    s = wave_sum_d(s);
+    if (threadIdx.x == 0) table[blockIdx.x] = blockIdx.x == 0 ? s / npix : s;
+}
+
+template <int KT, int V, typename TY>
+__global__ __launch_bounds__(256) void seg_stats_bwd_kernel(const float* __restrict__ logits, const TY* __restrict__ y,
+                                                           const float* __restrict__ class_w, const double* __restrict__ g_ce,
+                                                           const double* __restrict__ g_tp, const double* __restrict__ g_spr,
+                                                           float* __restrict__ dlogits, int K, int64_t HW, int64_t ngroups, double npix) {
+    double gt[KT], gs[KT], wc[KT];
+#pragma unroll
+    for (int c = 0; c < KT; ++c) {
+        gt[c] = (g_tp && c < K) ? g_tp[c] : 0.0;
+        gs[c] = (g_spr && c < K) ? g_spr[c] : 0.0;
+        wc[c] = (class_w && c < K) ? (double)class_w[c] : 1.0;
+    }
+    const double gce = g_ce ? g_ce[0] / npix : 0.0;
+    const int64_t gpi = HW / V;
+    const bool small = ngroups < (int64_t(1) << 31);
+    for (int64_t g = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; g < ngroups; g += (int64_t)gridDim.x * blockDim.x) {
+        const int64_t base = seg_group_base(g, gpi, small, K, HW, V);
+        SegVec<float, V> lv[KT], dv[KT];
+        SegVec<TY, V> yv[KT];
+#pragma unroll
+        for (int c = 0; c < KT; ++c)
+            if (c < K) {
+                lv[c] = *reinterpret_cast<const SegVec<float, V>*>(logits + base + c * HW);
+                yv[c] = *reinterpret_cast<const SegVec<TY, V>*>(y + base + c * HW);
+            }
+#pragma unroll
+        for (int v = 0; v < V; ++v) {
+            float l[KT], p[KT], lse;
+#pragma unroll
+            for (int c = 0; c < KT; ++c) l[c] = c < K ? lv[c].v[v] : 0.f;
+            seg_softmax<KT>(l, K, p, lse);
+            // dl_j = g_ce/npix * (p_j * sum_c w_c y_c - w_j y_j) + p_j * (G_j - sum_c p_c G_c), G_c = g_tp[c] y_c + g_spr[c]; fp64 from p on
+            double wy[KT], G[KT], swy = 0.0, spg = 0.0;
+#pragma unroll
+            for (int c = 0; c < KT; ++c)
+                if (c < K) {
+                    const double yc = (double)yv[c].v[v];
+                    wy[c] = wc[c] * yc;
+                    G[c] = gt[c] * yc + gs[c];
+                    swy += wy[c];
+                    spg += (double)p[c] * G[c];
+                }
+#pragma unroll
+            for (int c = 0; c < KT; ++c)
+                if (c < K) dv[c].v[v] = (float)(gce * ((double)p[c] * swy - wy[c]) + (double)p[c] * (G[c] - spg));
+        }
+#pragma unroll
+        for (int c = 0; c < KT; ++c)
+            if (c < K) *reinterpret_cast<SegVec<float, V>*>(dlogits + base + c * HW) = dv[c];
+    }
+}
+
+static inline int seg_grid(int64_t ngroups) {
+    const int64_t blocks = cmu_div_up64(ngroups, 256);
+    return (int)(blocks < CE_MAX_BLOCKS ? blocks : CE_MAX_BLOCKS);
+}
+// pixels per lane: 4 (2 at KT = 8, which keeps the K = 8 kernels clear of scratch) on whole 16-byte chunks of every plane, else 1
+static inline bool seg_vectorisable(int KT, int64_t HW, const void* a, const void* b, const void* c) {
+    return HW % (KT == 8 ? 2 : 4) == 0 && cmu_aligned16(a) && cmu_aligned16(b) && (c == nullptr || cmu_aligned16(c));
+}
+template <int KT, int V, typename TY>
+static void seg_fwd_launch(const float* logits, const void* y, const float* class_w, float thr, double* ws, int K, int64_t HW,
+                           int64_t npix, int grid, hipStream_t st) {
+    hipLaunchKernelGGL((seg_stats_kernel<KT, V, TY>), dim3(grid), dim3(256), 0, st, logits, (const TY*)y, class_w, thr, ws, K, HW, npix / V);
+}
+template <int KT, int V, typename TY>
+static void seg_bwd_launch(const float* logits, const void* y, const float* class_w, const double* g_ce, const double* g_tp,
+                           const double* g_spr, float* dlogits, int K, int64_t HW, int64_t npix, int grid, hipStream_t st) {
+    hipLaunchKernelGGL((seg_stats_bwd_kernel<KT, V, TY>), dim3(grid), dim3(256), 0, st, logits, (const TY*)y, class_w, g_ce, g_tp, g_spr,
+                       dlogits, K, HW, npix / V, (double)npix);
+}
+// FN<KT, V, TY>(args...) for the runtime class count, vector width and target type
+#define SEG_DISPATCH(FN, K, vec, f64, ...)                                                            \
+    do {                                                                                              \
+        if ((K) <= 2) {                                                                               \
+            if (vec) { if (f64) FN<2, 4, double>(__VA_ARGS__); else FN<2, 4, float>(__VA_ARGS__); }   \
+            else     { if (f64) FN<2, 1, double>(__VA_ARGS__); else FN<2, 1, float>(__VA_ARGS__); }   \
+        } else if ((K) <= 4) {                                                                        \
+            if (vec) { if (f64) FN<4, 4, double>(__VA_ARGS__); else FN<4, 4, float>(__VA_ARGS__); }   \
+            else     { if (f64) FN<4, 1, double>(__VA_ARGS__); else FN<4, 1, float>(__VA_ARGS__); }   \
+        } else {                                                                                      \
+            if (vec) { if (f64) FN<8, 2, double>(__VA_ARGS__); else FN<8, 2, float>(__VA_ARGS__); }   \
+            else     { if (f64) FN<8, 1, double>(__VA_ARGS__); else FN<8, 1, float>(__VA_ARGS__); }   \
+        }                                                                                             \
+    } while (0)
+
+extern "C" int64_t cmu_seg_stats_ws_bytes(int K) {
+    return (K < 2 || K > SEG_MAX_K) ? 0 : (int64_t)CE_MAX_BLOCKS * (1 + 5 * K) * (int64_t)sizeof(double);
+}
+extern "C" int cmu_seg_stats_fwd(const float* logits, const void* y, int y_is_f64, const float* class_w, float threshold, double* table,
+                                 int B, int K, int H, int W, void* ws, void* stream) {
+    CMU_CHECK_ARG(logits && y && table && ws && B > 0 && H > 0 && W > 0, "cmu_seg_stats_fwd: bad args");
+    CMU_CHECK_ARG(K >= 2 && K <= SEG_MAX_K, "cmu_seg_stats_fwd: 2 <= K <= %d classes (got %d)", SEG_MAX_K, K);
+    hipStream_t st = (hipStream_t)stream;
+    const int64_t HW = (int64_t)H * W, npix = (int64_t)B * HW;
+    const int KT = K <= 2 ? 2 : K <= 4 ? 4 : 8;
+    const bool vec = seg_vectorisable(KT, HW, logits, y, nullptr);
+    const int grid = seg_grid(npix / (vec ? (KT == 8 ? 2 : 4) : 1));
+    SEG_DISPATCH(seg_fwd_launch, K, vec, y_is_f64 != 0, logits, y, class_w, threshold, (double*)ws, K, HW, npix, grid, st);
+    CMU_CHECK_LAUNCH("cmu_seg_stats_fwd");
+    hipLaunchKernelGGL(seg_stats_final_kernel, dim3(1 + 5 * K), dim3(64), 0, st, (const double*)ws, grid, (double)npix, table);
+    CMU_CHECK_LAUNCH("cmu_seg_stats_fwd(final)");
+    return CMU_OK;
+}
+extern "C" int cmu_seg_stats_bwd(const float* logits, const void* y, int y_is_f64, const float* class_w, const double* g_ce,
+                                 const double* g_tp, const double* g_spr, float* dlogits, int B, int K, int H, int W, void* stream) {
+    CMU_CHECK_ARG(logits && y && dlogits && B > 0 && H > 0 && W > 0, "cmu_seg_stats_bwd: bad args");
+    CMU_CHECK_ARG(K >= 2 && K <= SEG_MAX_K, "cmu_seg_stats_bwd: 2 <= K <= %d classes (got %d)", SEG_MAX_K, K);
+    hipStream_t st = (hipStream_t)stream;
+    const int64_t HW = (int64_t)H * W, npix = (int64_t)B * HW;
+    const int KT = K <= 2 ? 2 : K <= 4 ? 4 : 8;
+    const bool vec = seg_vectorisable(KT, HW, logits, y, dlogits);
+    const int grid = seg_grid(npix / (vec ? (KT == 8 ? 2 : 4) : 1));
+    SEG_DISPATCH(seg_bwd_launch, K, vec, y_is_f64 != 0, logits, y, class_w, g_ce, g_tp, g_spr, dlogits, K, HW, npix, grid, st);
+    CMU_CHECK_LAUNCH("cmu_seg_stats_bwd");
+    return CMU_OK;
+}
+
+// ---------------------------------------------------------------------------------------------
 // L2 row normalisation (F.normalize(dim=1), eps 1e-12)
 // ---------------------------------------------------------------------------------------------
 __global__ __launch_bounds__(256) void l2norm_rows_kernel(const float* __restrict__ x, float* __restrict__ out, int D) {

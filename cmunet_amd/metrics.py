@@ -5,11 +5,20 @@ and ``IoU`` (:200-220), computed by ONE fused kernel per (prediction, target) pa
 ``cmu_softmax_ce_dice_fwd_bwd`` makes a single pass over the logits and yields the CE (with its gradient),
 and the thresholded Dice / IoU counters -- the reference makes 4-5 elementwise passes and a host sync each.
 
-Only the configuration the reference's driver uses is implemented on the HIP path (train.py:455-461:
-2 classes, activation 'softmax', threshold 0.5, ignore_channels [0], eps 1e-5 / 1e-7); other settings raise.
+The configuration the reference's driver uses (train.py:455-461: 2 classes, activation 'softmax', threshold 0.5, ignore_channels [0],
+eps 1e-5 / 1e-7) runs on that kernel.  Every other softmax configuration of the same classes -- 2..8 classes, ``threshold=None`` (the
+differentiable Dice / IoU: a Dice term that carries gradient) or any threshold, any ``ignore_channels`` / ``beta`` / ``eps``, per-class CE
+weights -- runs on ``cmu_seg_stats_fwd`` / ``cmu_seg_stats_bwd``: one pass per (prediction, target) pair and threshold yields per-class
+counters, the scores are a few fp64 flops on those K-vectors, and autograd through them hands the backward kernel its upstream
+gradients on the device.  Other activations raise.
+Which of the two kernels serves an object in the reference configuration on two-class logits depends on its context: inside a
+combined Loss, the fused two-class kernel only if every Dice / CE term of the combination is in that configuration (``_planned``);
+called on its own (a metric), the fused kernel unless the K-class pass has already run on the very same tensors (same objects,
+versions and grad mode) -- then its cached counters are reused, so the choice follows the call order, as train.py has it: loss first,
+metrics after.  Both kernels agree to rounding; only the reference configuration evaluated alone is bit-identical to earlier builds.
 ``hausdorff`` / ``radius_arteries`` (metrics.py:224-395: scikit-image contours and skeletons, scipy KD-trees on the host) run as
-exact lattice geometry on the device (csrc/geometry.hip): no ``.cpu()``, no host sync.
-The Dice term has no gradient, exactly like the reference's thresholded version (SURVEY A-4).
+exact lattice geometry on the device (csrc/geometry.hip): no ``.cpu()``, no host sync; two classes only.
+A thresholded Dice has no gradient, exactly like the reference's (SURVEY A-4).
 """
 import weakref
 
@@ -53,6 +62,9 @@ class Loss(BaseObject):
     def _terms(self):
         return [(1.0, self)]
 
+    def _leaves(self):
+        return [self]
+
     def __add__(self, other):
         if not isinstance(other, Loss):
             raise ValueError("Loss should be inherited from `Loss` class")
@@ -73,8 +85,11 @@ class SumOfLosses(Loss):
         super().__init__(name=f"{l1.__name__} + {l2.__name__}")
         self.l1, self.l2 = l1, l2
 
+    def _leaves(self):
+        return self.l1._leaves() + self.l2._leaves()
+
     def forward(self, *inputs):
-        return self.l1.forward(*inputs) + self.l2.forward(*inputs)
+        return _planned(self, inputs, lambda: self.l1.forward(*inputs) + self.l2.forward(*inputs))
 
     __call__ = forward
 
@@ -85,8 +100,11 @@ class MultipliedLoss(Loss):
         super().__init__(name=f"{multiplier} * ({inner})" if "+" in inner else f"{multiplier} * {inner}")
         self.loss, self.multiplier = loss, multiplier
 
+    def _leaves(self):
+        return self.loss._leaves()
+
     def forward(self, *inputs):
-        return self.multiplier * self.loss.forward(*inputs)
+        return _planned(self, inputs, lambda: self.multiplier * self.loss.forward(*inputs))
 
     __call__ = forward
 
@@ -120,10 +138,6 @@ class _SegStatsFn(torch.autograd.Function):
 _cache = {"pr": None, "gt": None, "ver": None, "out": None}
 
 
-def clear_seg_cache():
-    _cache.update(pr=None, gt=None, ver=None, out=None)
-
-
 def seg_stats(y_pr, y_gt):
     if not y_pr.is_cuda:
         raise RuntimeError("metrics: the HIP path needs CUDA/ROCm tensors (no CPU fallback)")
@@ -144,44 +158,233 @@ def _check_cfg(activation, threshold, ignore_channels, what):
                                   "(activation='softmax', threshold=0.5, ignore_channels=[0]; train.py:455-461)")
 
 
-class DiceLoss(Loss):
+# ---------------------------------------------------------------------------------------------------
+# any class count (2..8), threshold (None = the differentiable form), ignore_channels, beta, eps, class weights:
+# cmu_seg_stats_fwd / _bwd yield per-class counters, the scores are a few fp64 flops on K-element device tensors
+# ---------------------------------------------------------------------------------------------------
+def _kept(K, ignore_channels):
+    ign = sorted(set(int(c) for c in (ignore_channels or ())))
+    if any(c < 0 or c >= K for c in ign):
+        raise ValueError(f"ignore_channels {ign} out of range for {K} channels")
+    keep = [c for c in range(K) if c not in ign]
+    if not keep:
+        raise ValueError("ignore_channels leaves no channel")
+    return keep
+
+
+def _kept_sums(ignore_channels, *vectors):
+    K = vectors[0].shape[0]
+    keep = _kept(K, ignore_channels)
+    if len(keep) == K:
+        return [v.sum() for v in vectors]
+    # (element picks with Python indices: an index TENSOR built here would be a host-to-device copy, i.e. a host sync, per call)
+    return [torch.stack([v[c] for c in keep]).sum() for v in vectors]
+
+
+def f_score_from_counters(tp, spr, sgt, beta=1.0, eps=1e-5, ignore_channels=None):
+    """metrics.py:135-157 from per-class fp64 counters (K,) -- tp = sum gt*pr, spr = sum pr, sgt = sum gt, soft or thresholded --
+    over the channels that ``ignore_channels`` keeps.  Pure torch (CPU or device tensors), differentiable in tp / spr."""
+    tp, spr, sgt = _kept_sums(ignore_channels, tp, spr, sgt)
+    b2 = float(beta) ** 2
+    return ((1 + b2) * tp + eps) / ((1 + b2) * tp + b2 * (sgt - tp) + (spr - tp) + eps)
+
+
+def iou_from_counters(tp, spr, sgt, eps=1e-7, ignore_channels=None):
+    """metrics.py:182-198 from the same counters: (intersection + eps) / (sum gt + sum pr - intersection + eps)."""
+    tp, spr, sgt = _kept_sums(ignore_channels, tp, spr, sgt)
+    return (tp + eps) / (sgt + spr - tp + eps)
+
+
+class _SegTableFn(torch.autograd.Function):
+    """table = [ce | tp_soft | spr_soft | tp_hard | spr_hard | sgt] (1 + 5K fp64); the backward kernel takes the incoming gradients
+    of ce and of the soft counters straight from the device (the thresholded counters and sgt carry none)."""
+
+    @staticmethod
+    def forward(ctx, logits, y, class_w, threshold):
+        K = logits.shape[1]
+        table = torch.empty(1 + 5 * K, dtype=torch.float64, device=logits.device)
+        ws = torch.empty(_lib.lib().cmu_seg_stats_ws_bytes(K), dtype=torch.uint8, device=logits.device)
+        lg = logits.detach().contiguous()
+        ops.seg_stats_fwd(lg, y, class_w, threshold, table, ws)
+        ctx.save_for_backward(lg, y, class_w)
+        return table
+
+    @staticmethod
+    def backward(ctx, g):
+        lg, y, class_w = ctx.saved_tensors
+        K = lg.shape[1]
+        g = g.contiguous()
+        dl = torch.empty_like(lg)
+        ops.seg_stats_bwd(lg, y, class_w, g[0:1], g[1:1 + K], g[1 + K:1 + 2 * K], dl)
+        return dl, None, None, None
+
+
+DEFAULT_THRESHOLD = 0.5     # the threshold of a pass that only soft losses / the CE asked for
+_tables = {"pr": None, "gt": None, "ver": None, "entries": []}   # entries: (threshold, class weight or None, table)
+_plan = None                # set while a combined Loss evaluates its terms: {"legacy": bool, "weight": tensor or None}
+
+
+def _planned(loss, inputs, evaluate):
+    """Evaluate a combined Loss with its terms agreed on ONE pass: the parent's fused two-class kernel only if every Dice / CE term
+    is in the reference driver's configuration, and the class weights of its CE term known to the term that runs first."""
+    global _plan
+    if _plan is not None:
+        return evaluate()
+    seg = [l for l in loss._leaves() if hasattr(l, "_reference_cfg")]
+    ces = [l for l in seg if isinstance(l, CrossEntropyLoss)]
+    weight = None
+    if len(ces) == 1 and inputs and torch.is_tensor(inputs[0]) and inputs[0].is_cuda:
+        weight = ces[0]._weight_on(inputs[0].device)
+    _plan = {"legacy": all(l._reference_cfg for l in seg), "weight": weight}
+    try:
+        return evaluate()
+    finally:
+        _plan = None
+
+
+def clear_seg_cache():
+    _cache.update(pr=None, gt=None, ver=None, out=None)
+    _tables.update(pr=None, gt=None, ver=None, entries=[])
+
+
+def seg_table(y_pr, y_gt, threshold=None, class_w=None, any_weight=False):
+    """The counter table of the pair, from the cache when a pass with this threshold (``None``: any) and these class weights
+    (``any_weight``: any) has run on the same tensors; one pass per distinct threshold otherwise."""
+    if not y_pr.is_cuda:
+        raise RuntimeError("metrics: the HIP path needs CUDA/ROCm tensors (no CPU fallback)")
+    if y_pr.dim() != 4 or not 2 <= y_pr.shape[1] <= ops.SEG_MAX_K or y_gt.shape != y_pr.shape:
+        raise NotImplementedError(f"segmentation losses support (B,K,H,W) logits, 2 <= K <= {ops.SEG_MAX_K}, with targets of the same shape")
+    ver = (y_pr._version, y_gt._version, y_pr.requires_grad and torch.is_grad_enabled())
+    pr, gt = _tables["pr"], _tables["gt"]
+    if pr is None or pr() is not y_pr or gt() is not y_gt or _tables["ver"] != ver:
+        _tables.update(pr=weakref.ref(y_pr), gt=weakref.ref(y_gt), ver=ver, entries=[])
+    for t, w, table in _tables["entries"]:
+        if (threshold is None or t == threshold) and (any_weight or w is class_w):
+            return table
+    if any_weight and _plan is not None:
+        class_w = _plan["weight"]
+    if class_w is not None and class_w.shape[0] != y_pr.shape[1]:
+        raise ValueError(f"CrossEntropyLoss: {class_w.shape[0]} class weights for {y_pr.shape[1]} classes")
+    t = DEFAULT_THRESHOLD if threshold is None else threshold
+    y = y_gt if y_gt.dtype in (torch.float32, torch.float64) else y_gt.double()
+    table = _SegTableFn.apply(y_pr.float(), y.contiguous(), class_w, t)
+    _tables["entries"].append((t, class_w, table))
+    return table
+
+
+def _counters(table, threshold):
+    K = (table.shape[0] - 1) // 5
+    o = 1 if threshold is None else 1 + 2 * K
+    return table[o:o + K], table[o + K:o + 2 * K], table[1 + 4 * K:1 + 5 * K]
+
+
+def _check_seg_cfg(what, activation, threshold, ignore_channels, eps, beta=1.0):
+    if activation not in ("softmax", "softmax2d"):
+        raise NotImplementedError(f"{what}: activation 'softmax' / 'softmax2d' only on the HIP path (got {activation!r})")
+    if threshold is not None and not 0.0 < float(threshold) < 1.0:
+        raise ValueError(f"{what}: threshold must be None or inside (0, 1), got {threshold}")
+    if not eps > 0 or not beta > 0:
+        raise ValueError(f"{what}: eps and beta must be positive (got eps={eps}, beta={beta})")
+    _kept(ops.SEG_MAX_K, ignore_channels)
+
+
+def _pair_has_tables(y_pr, y_gt):
+    """A counter table of exactly this pair (same tensors, versions and grad mode) is in the cache."""
+    pr, gt = _tables["pr"], _tables["gt"]
+    return (pr is not None and pr() is y_pr and gt() is y_gt and bool(_tables["entries"])
+            and _tables["ver"] == (y_pr._version, y_gt._version, y_pr.requires_grad and torch.is_grad_enabled()))
+
+
+def _use_legacy(obj, y_pr, y_gt):
+    """The reference driver's configuration on two-class logits keeps the parent's fused kernel (the same bits as ever); inside a
+    combined Loss only when every Dice / CE term of it is in that configuration, so that the combination still costs one pass.
+    On its own (a metric), such an object reuses the counters of the pair when the loss before it ran the K-class pass on the same
+    tensors -- e.g. DiceLoss(threshold=None) + CrossEntropyLoss() on two classes -- instead of paying the fused kernel on top."""
+    if not (obj._reference_cfg and y_pr.dim() == 4 and y_pr.shape[1] == 2):
+        return False
+    return _plan["legacy"] if _plan is not None else not _pair_has_tables(y_pr, y_gt)
+
+
+class _SegScore:
+    """Shared by DiceLoss / DiceMetric / IoU: configuration and the loss value 1 - score from the pair's counters."""
+
+    def _configure(self, what, activation, threshold, ignore_channels, eps, beta, ref_eps):
+        _check_seg_cfg(what, activation, threshold, ignore_channels, eps, beta)
+        self.eps, self.beta, self.threshold = float(eps), float(beta), None if threshold is None else float(threshold)
+        self.activation, self.ignore_channels = activation, None if ignore_channels is None else list(ignore_channels)
+        self._reference_cfg = threshold == 0.5 and list(ignore_channels or []) == [0] and eps == ref_eps and beta == 1.0
+
+    def _dice(self, y_pr, y_gt):
+        tp, spr, sgt = _counters(seg_table(y_pr, y_gt, self.threshold, any_weight=True), self.threshold)
+        return 1.0 - f_score_from_counters(tp, spr, sgt, self.beta, self.eps, self.ignore_channels)
+
+    def _iou(self, y_pr, y_gt):
+        tp, spr, sgt = _counters(seg_table(y_pr, y_gt, self.threshold, any_weight=True), self.threshold)
+        return 1.0 - iou_from_counters(tp, spr, sgt, self.eps, self.ignore_channels)
+
+
+class DiceLoss(Loss, _SegScore):
+    """metrics.py:160-180.  ``threshold=None`` is the differentiable Dice (its gradient reaches the logits through
+    cmu_seg_stats_bwd); with a threshold the value is a step function of the logits and carries no gradient (SURVEY A-4)."""
+
     def __init__(self, eps=1e-5, beta=1.0, activation=None, ignore_channels=None, threshold=None, **kwargs):
         super().__init__(**kwargs)
-        _check_cfg(activation, threshold, ignore_channels, "DiceLoss")
-        if eps != 1e-5 or beta != 1.0:
-            raise NotImplementedError("DiceLoss: eps=1e-5, beta=1 only")
-        self.eps, self.beta, self.threshold, self.ignore_channels = eps, beta, threshold, ignore_channels
+        self._configure("DiceLoss", activation, threshold, ignore_channels, eps, beta, 1e-5)
 
     def forward(self, y_pr, y_gt):
-        return seg_stats(y_pr, y_gt)[1].detach().double()
+        if _use_legacy(self, y_pr, y_gt):
+            return seg_stats(y_pr, y_gt)[1].detach().double()
+        v = self._dice(y_pr, y_gt)
+        return v if self.threshold is None else v.detach()
 
 
 class CrossEntropyLoss(Loss):
-    """nn.CrossEntropyLoss() with probability (one-hot float) targets, mean over B*H*W (metrics.py:503)."""
+    """nn.CrossEntropyLoss(weight) with probability (one-hot float) targets, mean over B*H*W (metrics.py:503)."""
+
+    def __init__(self, weight=None, **kwargs):
+        super().__init__(**kwargs)
+        self.register_buffer("weight", None if weight is None else torch.as_tensor(weight, dtype=torch.float32).detach().clone().contiguous())
+        if self.weight is not None and self.weight.dim() != 1:
+            raise ValueError("CrossEntropyLoss: weight is a vector of one value per class")
+        self._reference_cfg = weight is None
+
+    def _weight_on(self, device):
+        """The weight buffer, moved to ``device`` once (the cache recognises a pass by the identity of its weight tensor)."""
+        if self.weight is not None and self.weight.device != device:
+            self.weight = self.weight.to(device)
+        return self.weight
 
     def forward(self, y_pr, y_gt):
-        return seg_stats(y_pr, y_gt)[0].double()
+        if _use_legacy(self, y_pr, y_gt):
+            return seg_stats(y_pr, y_gt)[0].double()
+        return seg_table(y_pr, y_gt, None, self._weight_on(y_pr.device))[0]
 
 
-class IoU(Metric):
+class IoU(Metric, _SegScore):
     __name__ = "iou_loss"
 
     def __init__(self, eps=1e-7, threshold=0.5, activation=None, ignore_channels=None, **kwargs):
         super().__init__(**kwargs)
-        _check_cfg(activation, threshold, ignore_channels, "IoU")
-        if eps != 1e-7:
-            raise NotImplementedError("IoU: eps=1e-7 only")
+        self._configure("IoU", activation, threshold, ignore_channels, eps, 1.0, 1e-7)
 
     def forward(self, y_pr, y_gt):
-        return seg_stats(y_pr, y_gt)[2].detach().double()
+        if _use_legacy(self, y_pr, y_gt):
+            return seg_stats(y_pr, y_gt)[2].detach().double()
+        return self._iou(y_pr, y_gt).detach()
 
 
-class DiceMetric(Metric):
+class DiceMetric(Metric, _SegScore):
     """The Dice loss value used as a metric (train.py:456-461 lists DiceLoss among the metrics)."""
     __name__ = "dice_loss"
 
+    def __init__(self, eps=1e-5, beta=1.0, activation="softmax", ignore_channels=(0,), threshold=0.5, **kwargs):
+        super().__init__(**kwargs)
+        self._configure("DiceMetric", activation, threshold, ignore_channels, eps, beta, 1e-5)
+
     def forward(self, y_pr, y_gt):
-        return seg_stats(y_pr, y_gt)[1].detach().double()
+        if _use_legacy(self, y_pr, y_gt):
+            return seg_stats(y_pr, y_gt)[1].detach().double()
+        return self._dice(y_pr, y_gt).detach()
 
 
 class soft_cldice(Loss):

@@ -401,6 +401,33 @@ def softmax_ce_dice_fwd_bwd(logits, y1h, out, dlogits, loss_scale, ws):
          _p(ws), _stream())
 
 
+SEG_MAX_K = 8
+
+
+def _seg_args(logits, y, class_w):
+    B, K, H, W = logits.shape
+    assert 2 <= K <= SEG_MAX_K and y.shape == logits.shape and y.is_contiguous() and y.dtype in (torch.float32, torch.float64)
+    assert class_w is None or (class_w.shape == (K,) and class_w.dtype == torch.float32 and class_w.is_contiguous())
+    return B, K, H, W
+
+
+def seg_stats_fwd(logits, y, class_w, threshold, table, ws):
+    """table (1 + 5K fp64) = [ce | tp_soft | spr_soft | tp_hard | spr_hard | sgt] of (B,K,H,W) fp32 logits and fp64 / fp32 targets."""
+    B, K, H, W = _seg_args(logits, y, class_w)
+    assert table.dtype == torch.float64 and table.numel() == 1 + 5 * K and table.is_contiguous()
+    call("cmu_seg_stats_fwd", _p(_f32c(logits)), _p(y), int(y.dtype == torch.float64), _p(class_w), float(threshold), _p(table),
+         B, K, H, W, _p(ws), _stream())
+
+
+def seg_stats_bwd(logits, y, class_w, g_ce, g_tp, g_spr, dlogits):
+    """dlogits (fp32) from the device-resident fp64 gradients w.r.t. ce (1) and the soft counters (K each); None = zeros."""
+    B, K, H, W = _seg_args(logits, y, class_w)
+    for g, n in ((g_ce, 1), (g_tp, K), (g_spr, K)):
+        assert g is None or (g.dtype == torch.float64 and g.numel() == n and g.is_contiguous())
+    call("cmu_seg_stats_bwd", _p(_f32c(logits)), _p(y), int(y.dtype == torch.float64), _p(class_w), _p(g_ce), _p(g_tp), _p(g_spr),
+         _p(_f32c(dlogits)), B, K, H, W, _stream())
+
+
 def infonce_inbatch_fwd_bwd(pred, keys, loss, dpred, rank, temperature, ct_weight):
     B, D = pred.shape
     call("cmu_infonce_inbatch_fwd_bwd", _p(_f32c(pred)), _p(_f32c(keys)), _p(loss), _p(dpred), B, keys.shape[0], D,

@@ -270,6 +270,31 @@ int64_t cmu_softmax_ce_dice_ws_bytes(int B, int H, int W);
 int cmu_softmax_ce_dice_fwd_bwd(const float* logits, const double* y1h, float* out, float* dlogits, float loss_scale,
                                 int B, int H, int W, void* ws, void* stream);
 
+/* Segmentation criterion for 2 <= K <= 8 classes (metrics.py:135-198,503 with any threshold / ignore_channels / beta / eps):
+ * ONE pass over logits (B,K,H,W) fp32 and targets y of the same shape (fp64 if y_is_f64, else fp32; one-hot or any probabilities)
+ * plus a fixed-order finalisation (no floating-point atomics: the same bits every run) writes table[1 + 5K] doubles:
+ *   table[0]            ce       = mean over B*H*W of -sum_c w_c y_c log_softmax(l)_c  (class_w: K fp32 weights, NULL = ones; the
+ *                                  divisor is the pixel count, as nn.CrossEntropyLoss(weight) has it for probability targets)
+ *   table[1      + c]   tp_soft  = sum y_c p_c          table[1 +  K + c]   spr_soft = sum p_c
+ *   table[1 + 2K + c]   tp_hard  = sum y_c [p_c > t]    table[1 + 3K + c]   spr_hard = sum [p_c > t]
+ *   table[1 + 4K + c]   sgt      = sum y_c
+ * with p = softmax(l, dim 1) in fp32 and t = threshold.  Every Dice / F-beta / IoU score, soft or thresholded at t, over any kept
+ * channels is a few flops on these vectors.  The access width is chosen for the WHOLE tensor, there is no vector body with a
+ * scalar tail: for K <= 4 a lane takes 4 consecutive pixels of every plane (16-byte logits loads, 2 x 16-byte fp64 target loads)
+ * when H*W % 4 == 0 and logits, y (and dlogits, backward) are 16-byte aligned; for K > 4 it takes 2 (8-byte logits / dlogits
+ * accesses, 16-byte fp64 target loads) when H*W % 2 == 0 and the same alignment holds; any other H*W or alignment sends every
+ * pixel down the one-pixel-per-lane path (4-byte accesses): same results, lower rate.  ws: cmu_seg_stats_ws_bytes(K) bytes.    */
+int64_t cmu_seg_stats_ws_bytes(int K);
+int cmu_seg_stats_fwd(const float* logits, const void* y, int y_is_f64, const float* class_w, float threshold, double* table,
+                      int B, int K, int H, int W, void* ws, void* stream);
+/* Backward of cmu_seg_stats_fwd in one pass: with the upstream gradients of the final loss w.r.t. ce (g_ce, 1 double) and the
+ * SOFT counters (g_tp[K], g_spr[K] doubles), all read from device memory (no host sync; a NULL pointer stands for zeros), and
+ * G_c = g_tp[c] y_c + g_spr[c]:
+ *   dlogits_j = g_ce / (B*H*W) * (p_j sum_c w_c y_c - w_j y_j) + p_j (G_j - sum_c p_c G_c)          (fp32, (B,K,H,W))
+ * p is the forward's fp32 softmax; the combination runs in fp64.  The thresholded counters carry no gradient (SURVEY A-4).     */
+int cmu_seg_stats_bwd(const float* logits, const void* y, int y_is_f64, const float* class_w, const double* g_ce,
+                      const double* g_tp, const double* g_spr, float* dlogits, int B, int K, int H, int W, void* stream);
+
 /* CM-UNet in-batch InfoNCE (cmunet_head.py:72-88): pred (B,D) raw predictor output (L2-normalised inside),
  * keys (N,D) gathered, already normalised target projections; label i + B*rank; loss = ct_w*2*t*CE.
  * dpred (nullable) = d loss / d pred (B,D).  loss: 1 + B floats (loss[0] total, loss[1+b] per-row terms).     */
