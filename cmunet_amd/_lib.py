@@ -31,6 +31,12 @@ _SIGS = {
     "cmu_soft_skeleton": (_I, [_P, _P, _I, _I, _I, _I, _P, _P]),
     "cmu_cldice_sums_ws_bytes": (_L, []),
     "cmu_cldice_sums": (_I, [_P, _P, _P, _P, _L, _P, _P, _P]),
+    "cmu_softmax_planes": (_I, [_P, _P, _I, _I, _I, _F, _P, _P, _I, _I, _I, _I, _P]),
+    "cmu_softmax_planes_bwd": (_I, [_P, _P, _I, _P, _I, _I, _I, _I, _P]),
+    "cmu_soft_skeleton_save_ws_bytes": (_L, [_L, _I]),
+    "cmu_soft_skeleton_save": (_I, [_P, _P, _I, _I, _I, _I, _P, _P]),
+    "cmu_soft_skeleton_bwd_ws_bytes": (_L, [_L]),
+    "cmu_soft_skeleton_bwd": (_I, [_P, _P, _P, _P, _P, _P, _P, _I, _I, _I, _I, _P, _P]),
     "cmu_argmax2_mask": (_I, [_P, _I, _P, _I, _I, _I, _I, _P]),
     "cmu_plane_mask": (_I, [_P, _I, _I, _I, _P, _I, _I, _I, _I, _P]),
     "cmu_contour_points_ws_bytes": (_L, [_I, _I, _I]),

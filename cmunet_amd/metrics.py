@@ -18,6 +18,7 @@ versions and grad mode) -- then its cached counters are reused, so the choice fo
 metrics after.  Both kernels agree to rounding; only the reference configuration evaluated alone is bit-identical to earlier builds.
 ``hausdorff`` / ``radius_arteries`` (metrics.py:224-395: scikit-image contours and skeletons, scipy KD-trees on the host) run as
 exact lattice geometry on the device (csrc/geometry.hip): no ``.cpu()``, no host sync; two classes only.
+``soft_cldice`` takes 2..8 classes too, and with ``threshold=None`` it is a differentiable loss.
 A thresholded Dice has no gradient, exactly like the reference's (SURVEY A-4).
 """
 import weakref
@@ -387,26 +388,79 @@ class DiceMetric(Metric, _SegScore):
         return self._dice(y_pr, y_gt).detach()
 
 
+def _cldice_planes_sums(logits, y, keep, threshold, num_iter, save):
+    """(four clDice sums (fp32, device), what a backward needs or None): planes of the kept channels -> both soft skeletons -> sums."""
+    B, K, H, W = logits.shape
+    dev = logits.device
+    yp = torch.empty(B * len(keep), H, W, dtype=torch.float32, device=dev)
+    yt = torch.empty_like(yp)
+    ops.softmax_planes(logits, y, keep, threshold, yp, yt)
+    sp, st = torch.empty_like(yp), torch.empty_like(yp)
+    ws = torch.empty(_lib.lib().cmu_soft_skeleton_ws_bytes(yp.numel()), dtype=torch.uint8, device=dev)
+    kept = ops.soft_skeleton_save(yp, sp, num_iter) if save else ops.soft_skeleton(yp, sp, num_iter, ws)
+    ops.soft_skeleton(yt, st, num_iter, ws)
+    out4 = torch.empty(4, dtype=torch.float32, device=dev)
+    ops.cldice_sums(sp, yt, st, yp, out4)
+    return out4, ((yp, yt, st, kept) if save else None)
+
+
+class _ClDiceSumsFn(torch.autograd.Function):
+    """The four sums of the soft (threshold=None) clDice as fp64; the backward takes their incoming gradients g0..g3 straight from
+    the device: dL/dskel_pred = g0 y_true + g1 runs down the skeleton's levels (cmu_soft_skeleton_bwd, which also adds the sums' own
+    term g2 skel_true), and cmu_softmax_planes_bwd carries the planes' gradient to the logits.  The target has no gradient."""
+
+    @staticmethod
+    def forward(ctx, logits, y, keep, num_iter):
+        lg = logits.detach().contiguous()
+        out4, saved = _cldice_planes_sums(lg, y, keep, None, num_iter, True)
+        ctx.save_for_backward(lg, *saved)
+        ctx.keep, ctx.num_iter = keep, num_iter
+        return out4.double()
+
+    @staticmethod
+    def backward(ctx, g):
+        lg, yp, yt, st, kept = ctx.saved_tensors
+        G = torch.empty_like(yp)
+        ops.soft_skeleton_bwd(yp, kept, ctx.num_iter, G, g4=g.contiguous(), y_true=yt, skel_true=st)
+        dl = torch.empty_like(lg)
+        ops.softmax_planes_bwd(lg, G, ctx.keep, dl)
+        return dl, None, None, None
+
+
 class soft_cldice(Loss):
-    """Soft clDice (metrics.py:401-431) evaluated on the device: binarised foreground -> soft skeletons of prediction and
-    target by ten rounds of min/max pooling (cmu_soft_skeleton) -> four sums (cmu_cldice_sums) -> 1 - 2*tprec*tsens/(tprec+tsens).
-    The configuration of the reference's driver (train.py:464: activation 'softmax', threshold 0.5, ignore_channels [0],
-    two classes) runs on the HIP path; other settings raise.  Thresholded -> no gradient, as in the reference."""
+    """Soft clDice (metrics.py:401-431) on the device: softmax -> kept channels (``ignore_channels``, then ``exclude_background``
+    drops the first channel left) -> soft skeletons of prediction and target by ``num_iter`` = 10 rounds of min/max pooling -> four
+    sums (cmu_cldice_sums) -> 1 - 2*tprec*tsens/(tprec+tsens) in fp64.  2..8 classes.
+    ``threshold=None`` is the differentiable loss: its gradient reaches the logits through one autograd.Function (a reverse sweep over
+    the skeleton's levels and a softmax backward, csrc/cldice_grad.hip); nothing is kept for a backward under
+    ``no_grad`` or for logits that need no gradient.  With a threshold the skeletons are those of the binarised prediction and the
+    value carries no gradient, as in the reference; the driver's configuration (train.py:464: a threshold, ignore_channels [0]) on
+    two-class logits runs its own kernel sequence (cmu_softmax2_threshold) as before.  Other activations raise."""
     __name__ = "soft_clDice"
 
     def __init__(self, iter_=3, smooth=1., exclude_background=False, threshold=0.5, activation=None, ignore_channels=None):
         super().__init__()
-        if activation not in ("softmax", "softmax2d") or threshold is None or list(ignore_channels or []) != [0] or exclude_background:
-            raise NotImplementedError("soft_cldice: only the reference driver's configuration (activation='softmax', a threshold, "
-                                      "ignore_channels=[0]) is implemented on the HIP path")
-        self.iter, self.smooth, self.threshold, self.num_iter = iter_, smooth, float(threshold), 10
+        if activation not in ("softmax", "softmax2d"):
+            raise NotImplementedError(f"soft_cldice: activation 'softmax' / 'softmax2d' only on the HIP path (got {activation!r})")
+        if not smooth > 0:
+            raise ValueError(f"soft_cldice: smooth must be positive (got {smooth})")
+        _kept(ops.SEG_MAX_K, ignore_channels)
+        self.iter, self.smooth, self.num_iter = iter_, smooth, 10      # (iter_ is unused in the reference too: SoftSkeletonize(num_iter=10))
+        self.threshold = None if threshold is None else float(threshold)
+        self.activation, self.exclude_background = activation, bool(exclude_background)
+        self.ignore_channels = None if ignore_channels is None else list(ignore_channels)
 
-    def forward(self, y_pred, y_true):
-        if not y_pred.is_cuda:
-            raise RuntimeError("soft_cldice runs on the GPU only (no CPU fallback)")
+    def _keep(self, K):
+        keep = _kept(K, self.ignore_channels)
+        if self.exclude_background:
+            keep = keep[1:]
+            if not keep:
+                raise ValueError("soft_cldice: exclude_background leaves no channel")
+        return keep
+
+    def _driver_sums(self, y_pred, y_true):
+        """The driver's thresholded configuration on two classes: the kernel sequence (and the bits) it has always had."""
         B, K, H, W = y_pred.shape
-        if K != 2:
-            raise NotImplementedError("soft_cldice: two-class logits expected")
         logits = y_pred.detach().float().contiguous()
         yt = y_true[:, 1].detach().float().contiguous()
         yp = torch.empty(B, H, W, dtype=torch.float32, device=y_pred.device)
@@ -417,7 +471,24 @@ class soft_cldice(Loss):
         ops.soft_skeleton(yt, st, self.num_iter, ws)
         out4 = torch.empty(4, dtype=torch.float32, device=y_pred.device)
         ops.cldice_sums(sp, yt, st, yp, out4)
-        s = out4.double()
+        return out4.double()
+
+    def forward(self, y_pred, y_true):
+        if not y_pred.is_cuda:
+            raise RuntimeError("soft_cldice runs on the GPU only (no CPU fallback)")
+        if y_pred.dim() != 4 or not 2 <= y_pred.shape[1] <= ops.SEG_MAX_K or y_true.shape != y_pred.shape:
+            raise NotImplementedError(f"soft_cldice: (B,K,H,W) logits, 2 <= K <= {ops.SEG_MAX_K}, with targets of the same shape")
+        K = y_pred.shape[1]
+        keep = self._keep(K)
+        if self.threshold is not None and K == 2 and keep == [1] and not self.exclude_background:
+            s = self._driver_sums(y_pred, y_true)
+        else:
+            y = y_true.detach()
+            y = (y if y.dtype in (torch.float32, torch.float64) else y.float()).contiguous()
+            if self.threshold is None and y_pred.requires_grad and torch.is_grad_enabled():
+                s = _ClDiceSumsFn.apply(y_pred.float(), y, keep, int(self.num_iter))
+            else:
+                s = _cldice_planes_sums(y_pred.detach().float().contiguous(), y, keep, self.threshold, int(self.num_iter), False)[0].double()
         tprec = (s[0] + self.smooth) / (s[1] + self.smooth)
         tsens = (s[2] + self.smooth) / (s[3] + self.smooth)
         return 1. - 2.0 * (tprec * tsens) / (tprec + tsens)

@@ -519,6 +519,64 @@ def soft_skeleton(img, skel, num_iter, ws=None):
     call("cmu_soft_skeleton", _p(_f32c(img)), _p(_f32c(skel)), P, H, W, int(num_iter), _p(ws), _stream())
 
 
+def keep_mask(keep):
+    """Bit k set for every kept channel k (the planes kernels take the channel list as a mask: no device-side index array)."""
+    m = 0
+    for c in keep:
+        m |= 1 << int(c)
+    return m
+
+
+def softmax_planes(logits, target, keep, threshold, p_planes, t_planes):
+    """softmax(dim=1) of the channels ``keep`` of (B,K,H,W) fp32 logits as (B*Kk,H,W) fp32 planes (``threshold``: p > threshold as
+    0/1), and the same channels of the fp32 / fp64 target (``target`` and ``t_planes`` may both be None)."""
+    B, K, H, W = logits.shape
+    keep = list(keep)
+    assert 2 <= K <= SEG_MAX_K and keep and keep == sorted(set(keep)) and 0 <= keep[0] and keep[-1] < K
+    assert p_planes.numel() == B * len(keep) * H * W and (target is None) == (t_planes is None)
+    if target is not None:
+        assert target.shape == logits.shape and target.is_contiguous() and target.dtype in (torch.float32, torch.float64)
+        assert t_planes.numel() == p_planes.numel()
+        _f32c(t_planes)
+    call("cmu_softmax_planes", _p(_f32c(logits)), _p(target), int(target is not None and target.dtype == torch.float64), keep_mask(keep),
+         int(threshold is not None), float(threshold or 0.0), _p(_f32c(p_planes)), _p(t_planes), B, K, H, W, _stream())
+
+
+def softmax_planes_bwd(logits, g_planes, keep, dlogits):
+    """dlogits_k = p_k (G_k - sum_j p_j G_j), G = ``g_planes`` (B*Kk,H,W) on the channels ``keep`` and zero elsewhere."""
+    B, K, H, W = logits.shape
+    keep = list(keep)
+    assert 2 <= K <= SEG_MAX_K and keep and keep == sorted(set(keep)) and 0 <= keep[0] and keep[-1] < K
+    assert g_planes.numel() == B * len(keep) * H * W and dlogits.shape == logits.shape
+    call("cmu_softmax_planes_bwd", _p(_f32c(logits)), _p(_f32c(g_planes)), keep_mask(keep), _p(_f32c(dlogits)), B, K, H, W, _stream())
+
+
+def soft_skeleton_save(img, skel, num_iter, kept=None):
+    """``soft_skeleton`` (the same bits) that keeps its level images and running skeletons for ``soft_skeleton_bwd``; returns them."""
+    P, H, W = img.shape
+    if kept is None:
+        kept = torch.empty(_lib.lib().cmu_soft_skeleton_save_ws_bytes(img.numel(), int(num_iter)), dtype=torch.uint8, device=img.device)
+    assert kept.numel() >= _lib.lib().cmu_soft_skeleton_save_ws_bytes(img.numel(), int(num_iter)) and skel.shape == img.shape
+    call("cmu_soft_skeleton_save", _p(_f32c(img)), _p(_f32c(skel)), P, H, W, int(num_iter), _p(kept), _stream())
+    return kept
+
+
+def soft_skeleton_bwd(img, kept, num_iter, dimg, g_skel=None, g4=None, y_true=None, skel_true=None, ws=None):
+    """dimg = gradient of <g, soft_skeleton(img)> w.r.t. ``img`` (P,H,W), g = ``g_skel`` and / or the clDice tail of the device-resident
+    fp64 ``g4`` (g4[0] * y_true + g4[1]; ``dimg`` then gains g4[2] * skel_true).  ``kept`` comes from ``soft_skeleton_save``."""
+    P, H, W = img.shape
+    assert g_skel is not None or g4 is not None
+    assert kept.numel() >= _lib.lib().cmu_soft_skeleton_save_ws_bytes(img.numel(), int(num_iter)) and dimg.shape == img.shape
+    for t in (g_skel, y_true, skel_true):
+        assert t is None or (t.numel() == img.numel() and _f32c(t) is t)
+    if g4 is not None:
+        assert g4.dtype == torch.float64 and g4.numel() == 4 and g4.is_contiguous() and y_true is not None and skel_true is not None
+    if ws is None:
+        ws = torch.empty(_lib.lib().cmu_soft_skeleton_bwd_ws_bytes(img.numel()), dtype=torch.uint8, device=img.device)
+    call("cmu_soft_skeleton_bwd", _p(_f32c(img)), _p(kept), _p(g_skel), _p(g4), _p(y_true), _p(skel_true), _p(_f32c(dimg)), P, H, W,
+         int(num_iter), _p(ws), _stream())
+
+
 def cldice_sums(skel_pred, y_true, skel_true, y_pred, out4, ws=None):
     """out4 = (sum skel_pred*y_true, sum skel_pred, sum skel_true*y_pred, sum skel_true) over same-sized fp32 tensors."""
     if ws is None:

@@ -521,6 +521,30 @@ int64_t cmu_cldice_sums_ws_bytes(void);
 int cmu_cldice_sums(const float* skel_pred, const float* y_true, const float* skel_true, const float* y_pred, int64_t n,
                     float* out4, void* ws, void* stream);
 
+/* The differentiable soft-clDice (threshold=None; csrc/cldice_grad.hip).  Planes are fp32 (B*Kk, H, W): the Kk channels that bit k of
+ * keep_mask keeps, in ascending order, image by image.
+ *   cmu_softmax_planes      p_planes = softmax(logits, dim=1) of the kept channels (use_threshold: p > threshold as 0/1); t_planes =
+ *                           the same channels of the f32 / f64 (B,K,H,W) target (target and t_planes may both be NULL).  2 <= K <= 8.
+ *   cmu_softmax_planes_bwd  dlogits_k = p_k (G_k - sum_j p_j G_j) with G = g_planes on the kept channels and 0 elsewhere; p is
+ *                           recomputed by the forward's instruction sequence (the same bits).
+ *   cmu_soft_skeleton_save  the bits of cmu_soft_skeleton; `kept` (cmu_soft_skeleton_save_ws_bytes) receives the level images
+ *                           img_1..img_{num_iter+1}, the running skeletons skel_0..skel_{num_iter-1} ((2 num_iter + 1) n floats) and
+ *                           one selection-code byte per pixel for every dilate and every erode window (2 (num_iter + 1) n bytes).
+ *   cmu_soft_skeleton_bwd   dimg = d/dimg of <g, soft_skeleton(img)> by one reverse sweep over the levels in gather form (no atomics:
+ *                           the same bits on every call), PyTorch autograd's sub-gradients (first maximum / first minimum of a pooling
+ *                           window, equal column and row minima share the gradient, relu'(0) = 0).  g = g_skel (may be NULL) plus,
+ *                           with the device-resident fp64 g4 = dL/d(the four sums of cmu_cldice_sums), g4[0] y_true + g4[1]; dimg then
+ *                           also gains g4[2] skel_true.  ws: cmu_soft_skeleton_bwd_ws_bytes(n).                                    */
+int cmu_softmax_planes(const float* logits, const void* target, int target_is_f64, int keep_mask, int use_threshold, float threshold,
+                       float* p_planes, float* t_planes, int B, int K, int H, int W, void* stream);
+int cmu_softmax_planes_bwd(const float* logits, const float* g_planes, int keep_mask, float* dlogits, int B, int K, int H, int W,
+                           void* stream);
+int64_t cmu_soft_skeleton_save_ws_bytes(int64_t n, int num_iter);
+int cmu_soft_skeleton_save(const float* img, float* skel, int planes, int H, int W, int num_iter, void* kept, void* stream);
+int64_t cmu_soft_skeleton_bwd_ws_bytes(int64_t n);
+int cmu_soft_skeleton_bwd(const float* img, const void* kept, const float* g_skel, const double* g4, const float* y_true,
+                          const float* skel_true, float* dimg, int planes, int H, int W, int num_iter, void* ws, void* stream);
+
 /* Geometry metrics of the finetuning driver (Finetuning/train.py:462-463: hausdorff, radius_arteries; metrics.py:224-395, where
  * scikit-image's find_contours / skeletonize and scipy KD-trees run on the host per image) as exact lattice geometry
  * (csrc/geometry.hip).  Masks are uint8 (B,H,W) 0/1.  The doubled lattice of an H x W mask has (2H-1) x (2W-1) points: pixel
