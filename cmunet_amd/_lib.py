@@ -119,6 +119,12 @@ _SIGS = {
     "cmu_seg_stats_ws_bytes": (_L, [_I]),
     "cmu_seg_stats_fwd": (_I, [_P, _P, _I, _P, _F, _P, _I, _I, _I, _I, _P, _P]),
     "cmu_seg_stats_bwd": (_I, [_P, _P, _I, _P, _P, _P, _P, _P, _I, _I, _I, _I, _P]),
+    "cmu_pointwise_loss_ws_bytes": (_L, []),
+    "cmu_pointwise_loss_fwd": (_I, [_I, _P, _P, _I, _P, _P, _P, _L, _I, _L, _P, _P]),
+    "cmu_pointwise_loss_bwd": (_I, [_I, _P, _P, _I, _P, _P, _P, _P, _L, _I, _L, _P]),
+    "cmu_index_ce_ws_bytes": (_L, []),
+    "cmu_index_ce_fwd": (_I, [_P, _P, _I, _I, _I, _P, _L, _P, _I, _I, _I, _I, _P, _P]),
+    "cmu_index_ce_bwd": (_I, [_P, _P, _I, _I, _I, _P, _L, _P, _P, _I, _I, _I, _I, _P]),
     "cmu_infonce_inbatch_fwd_bwd": (_I, [_P, _P, _P, _P, _I, _I, _I, _I, _F, _F, _P]),
     "cmu_moco_ws_bytes": (_L, [_I, _I, _I]),
     "cmu_moco_infonce_enqueue": (_I, [_P, _P, _P, _I, _P, _P, _P, _P, _P, _I, _I, _I, _F, _P, _P]),

@@ -20,6 +20,16 @@ metrics after.  Both kernels agree to rounding; only the reference configuration
 exact lattice geometry on the device (csrc/geometry.hip): no ``.cpu()``, no host sync; two classes only.
 ``soft_cldice`` takes 2..8 classes too, and with ``threshold=None`` it is a differentiable loss.
 A thresholded Dice has no gradient, exactly like the reference's (SURVEY A-4).
+The rest of the reference's loss surface (metrics.py:495-551), each a ``Loss`` that returns a 0-dim fp64 device
+tensor and composes with ``+`` and a numeric factor:
+``L1Loss(reduction)``, ``MSELoss(reduction)``, ``BCELoss(weight, reduction)`` and ``BCEWithLogitsLoss(weight, reduction, pos_weight)``
+-- the criterion of a one-channel binary head, ``UNet(out_classes=1)`` -- run on ``cmu_pointwise_loss_fwd`` / ``_bwd``: one streaming
+pass yields the fp64 sum, one more the gradient from the device-resident upstream gradient; ``reduction`` is 'mean' or 'sum' ('none'
+raises), ``weight`` / ``pos_weight`` are one element or per channel ((C,1,1) / (1,C,1,1), C <= 8).
+``RobustCrossEntropyLoss(weight, ignore_index, reduction, label_smoothing)`` takes CLASS-INDEX targets ((B,1,H,W) or (B,H,W) label maps
+of int64 / int32 / uint8 / fp32 / fp64, read in their own dtype: 1-8 bytes per pixel instead of the 8K of fp64 one-hot planes) and
+``NLLLoss(activation, ignore_channels, threshold)`` one-hot targets whose arg-max over the kept channels is taken in the kernel; both run
+on ``cmu_index_ce_fwd`` / ``_bwd`` (2..8 classes), which yield three fp64 sums from which torch's reductions follow on the device.
 """
 import weakref
 
@@ -670,3 +680,232 @@ class radius_arteries(Metric):
     def forward(self, y_pr, y_gt):
         r = self.per_image(y_pr, y_gt)
         return (r[:, 0, 1] - r[:, 1, 1]).abs().mean()
+
+
+# ---------------------------------------------------------------------------------------------------
+# the rest of the reference's loss surface (metrics.py:495-551): L1Loss, MSELoss, BCELoss, BCEWithLogitsLoss (one-channel binary
+# heads) on cmu_pointwise_loss_fwd / _bwd; NLLLoss and RobustCrossEntropyLoss (class-index targets) on cmu_index_ce_fwd / _bwd
+# (csrc/pointwise_loss.hip)
+# ---------------------------------------------------------------------------------------------------
+def _check_device(what, *tensors):
+    if not all(t.is_cuda for t in tensors):
+        raise RuntimeError(f"{what} runs on the GPU only (no CPU fallback)")
+
+
+def _check_reduction(what, reduction):
+    if reduction == "none":
+        raise NotImplementedError(f"{what}: reduction 'mean' / 'sum' on the HIP path (the kernels return sums, not per-element values)")
+    if reduction not in ("mean", "sum"):
+        raise ValueError(f"{what}: {reduction!r} is not a valid value for reduction")
+    return reduction
+
+
+def _float_target(y):
+    y = y.detach()
+    return (y if y.dtype in (torch.float32, torch.float64) else y.double()).contiguous()
+
+
+class _PointwiseSumFn(torch.autograd.Function):
+    """S = sum_i w_c term_i as a 0-dim fp64 device tensor; the backward kernel reads its incoming gradient from the device."""
+
+    @staticmethod
+    def forward(ctx, x, y, kind, chan_w, chan_pw):
+        xc = x.detach().contiguous()
+        out = torch.empty(1, dtype=torch.float64, device=x.device)
+        ws = torch.empty(_lib.lib().cmu_pointwise_loss_ws_bytes(), dtype=torch.uint8, device=x.device)
+        ops.pointwise_loss_fwd(kind, xc, y, chan_w, chan_pw, out, ws)
+        ctx.save_for_backward(xc, y, chan_w, chan_pw)
+        ctx.kind = kind
+        return out[0]
+
+    @staticmethod
+    def backward(ctx, g):
+        xc, y, chan_w, chan_pw = ctx.saved_tensors
+        dx = torch.empty_like(xc)
+        ops.pointwise_loss_bwd(ctx.kind, xc, y, chan_w, chan_pw, g.reshape(1).contiguous(), dx)
+        return dx, None, None, None, None
+
+
+def _pointwise(what, kind, reduction, y_pr, y_gt, chan_w=None, chan_pw=None):
+    _check_device(what, y_pr, y_gt)
+    if y_pr.shape != y_gt.shape:
+        raise ValueError(f"{what}: target size {tuple(y_gt.shape)} must be the same as input size {tuple(y_pr.shape)}")
+    if y_pr.numel() == 0:
+        raise ValueError(f"{what}: empty input")
+    s = _PointwiseSumFn.apply(y_pr.float(), _float_target(y_gt), kind, chan_w, chan_pw)
+    return s / float(y_pr.numel()) if reduction == "mean" else s
+
+
+class L1Loss(Loss):
+    """nn.L1Loss(reduction) (metrics.py:495) on two tensors of one shape; fp32 or fp64 targets."""
+
+    def __init__(self, reduction="mean", **kwargs):
+        super().__init__(**kwargs)
+        self.reduction = _check_reduction("L1Loss", reduction)
+
+    def forward(self, y_pr, y_gt):
+        return _pointwise("L1Loss", "l1", self.reduction, y_pr, y_gt)
+
+
+class MSELoss(Loss):
+    """nn.MSELoss(reduction) (metrics.py:499)."""
+
+    def __init__(self, reduction="mean", **kwargs):
+        super().__init__(**kwargs)
+        self.reduction = _check_reduction("MSELoss", reduction)
+
+    def forward(self, y_pr, y_gt):
+        return _pointwise("MSELoss", "mse", self.reduction, y_pr, y_gt)
+
+
+def _channel_weight(what, name, w):
+    """None, or the weight as an fp32 vector: one element (a factor on everything) or one per channel, from the shapes that
+    broadcast per channel against (B,C,H,W) in torch: (C,1,1) and (1,C,1,1)."""
+    if w is None:
+        return None
+    w = torch.as_tensor(w, dtype=torch.float32).detach().clone()
+    per_channel = (w.dim() == 3 and w.shape[1:] == (1, 1)) or (w.dim() == 4 and w.shape[0] == 1 and w.shape[2:] == (1, 1))
+    if w.numel() != 1 and not per_channel:
+        raise NotImplementedError(f"{what}: {name} of shape {tuple(w.shape)}: one element, (C,1,1) or (1,C,1,1) on the HIP path")
+    if w.numel() > ops.PWL_MAX_C:
+        raise NotImplementedError(f"{what}: {name} over {w.numel()} channels (at most {ops.PWL_MAX_C})")
+    return w.reshape(-1).contiguous()
+
+
+class _ChannelWeighted(Loss):
+    """Shared by the two BCE classes: the per-channel vectors the kernel takes, fitted to the input's channel count."""
+
+    def _vectors(self, what, y_pr):
+        for name in ("weight", "pos_weight"):               # moved to the input's device once, as CrossEntropyLoss._weight_on
+            v = getattr(self, name, None)
+            if v is not None and v.device != y_pr.device:
+                setattr(self, name, v.to(y_pr.device))
+        vs = [v for v in (self.weight, getattr(self, "pos_weight", None)) if v is not None]
+        if not vs:
+            return None, None
+        C = max(v.numel() for v in vs)
+        if C > 1 and (y_pr.dim() != 4 or y_pr.shape[1] != C):
+            raise ValueError(f"{what}: weights over {C} channels against an input of shape {tuple(y_pr.shape)}")
+        return tuple(None if v is None else (v if v.numel() == C else v.expand(C).contiguous()) for v in (self.weight, getattr(self, "pos_weight", None)))
+
+
+class BCELoss(_ChannelWeighted):
+    """nn.BCELoss(weight, reduction) (metrics.py:546) on probabilities: (B,C,H,W) with 1 <= C <= 8, or any shape without a
+    per-channel weight.  A prediction outside [0, 1] gives NaN (torch raises; that would need a host sync)."""
+
+    def __init__(self, weight=None, reduction="mean", **kwargs):
+        super().__init__(**kwargs)
+        self.register_buffer("weight", _channel_weight("BCELoss", "weight", weight))
+        self.reduction = _check_reduction("BCELoss", reduction)
+
+    def forward(self, y_pr, y_gt):
+        _check_device("BCELoss", y_pr, y_gt)
+        w, _ = self._vectors("BCELoss", y_pr)
+        return _pointwise("BCELoss", "bce", self.reduction, y_pr, y_gt, w)
+
+
+class BCEWithLogitsLoss(_ChannelWeighted):
+    """nn.BCEWithLogitsLoss(weight, reduction, pos_weight) (metrics.py:550): the criterion of a one-channel binary head
+    (UNet(out_classes=1)); finite for any logit."""
+
+    def __init__(self, weight=None, reduction="mean", pos_weight=None, **kwargs):
+        super().__init__(**kwargs)
+        self.register_buffer("weight", _channel_weight("BCEWithLogitsLoss", "weight", weight))
+        self.register_buffer("pos_weight", _channel_weight("BCEWithLogitsLoss", "pos_weight", pos_weight))
+        self.reduction = _check_reduction("BCEWithLogitsLoss", reduction)
+
+    def forward(self, y_pr, y_gt):
+        _check_device("BCEWithLogitsLoss", y_pr, y_gt)
+        w, pw = self._vectors("BCEWithLogitsLoss", y_pr)
+        return _pointwise("BCEWithLogitsLoss", "bce_with_logits", self.reduction, y_pr, y_gt, w, pw)
+
+
+class _IndexCEFn(torch.autograd.Function):
+    """table = [sum w_t (-log p_t) | sum w_t | sum_kept w_c (-log p_c)] (3 fp64); the backward kernel takes the incoming gradients
+    of table[0] and table[2] from the device (table[1] does not depend on the input)."""
+
+    @staticmethod
+    def forward(ctx, x, target, onehot, log_input, keep, class_w, ignore_index):
+        xc = x.detach().contiguous()
+        table = torch.empty(3, dtype=torch.float64, device=x.device)
+        ws = torch.empty(_lib.lib().cmu_index_ce_ws_bytes(), dtype=torch.uint8, device=x.device)
+        ops.index_ce_fwd(xc, target, onehot, log_input, keep, class_w, ignore_index, table, ws)
+        ctx.save_for_backward(xc, target, class_w)
+        ctx.cfg = (onehot, log_input, keep, ignore_index)
+        return table
+
+    @staticmethod
+    def backward(ctx, g):
+        xc, target, class_w = ctx.saved_tensors
+        onehot, log_input, keep, ignore_index = ctx.cfg
+        dx = torch.empty_like(xc)
+        ops.index_ce_bwd(xc, target, onehot, log_input, keep, class_w, ignore_index, torch.stack((g[0], g[2])), dx)
+        return dx, None, None, None, None, None, None
+
+
+def _check_index_input(what, y_pr):
+    if y_pr.dim() != 4 or not 2 <= y_pr.shape[1] <= ops.SEG_MAX_K:
+        raise NotImplementedError(f"{what}: (B,K,H,W) input with 2 <= K <= {ops.SEG_MAX_K} (got shape {tuple(y_pr.shape)})")
+
+
+class NLLLoss(Loss):
+    """metrics.py:523-543: activation -> drop ``ignore_channels`` from prediction and target -> arg-max of the kept one-hot target
+    channels -> nn.NLLLoss() (mean over pixels), as one pass: 'logsoftmax' (nn.LogSoftmax()'s implicit dim is 1 for a 4-D input,
+    which is required here) takes the log-softmax over all K channels in the kernel, None / 'identity' reads log-probabilities.
+    ``threshold`` is stored and unused, as in the reference."""
+
+    def __init__(self, activation=None, ignore_channels=None, threshold=None, **kwargs):
+        super().__init__(**kwargs)
+        if activation not in (None, "identity", "logsoftmax"):
+            raise NotImplementedError(f"NLLLoss: activation 'logsoftmax', 'identity' or None on the HIP path (got {activation!r})")
+        _kept(ops.SEG_MAX_K, ignore_channels)
+        self.activation, self.threshold = activation, threshold
+        self.ignore_channels = None if ignore_channels is None else list(ignore_channels)
+
+    def forward(self, y_pr, y_gt):
+        _check_device("NLLLoss", y_pr, y_gt)
+        _check_index_input("NLLLoss", y_pr)
+        if y_gt.shape != y_pr.shape:
+            raise NotImplementedError("NLLLoss: one-hot targets of the prediction's shape")
+        keep = _kept(y_pr.shape[1], self.ignore_channels)
+        y = y_gt.detach()
+        y = (y if y.dtype in (torch.float32, torch.float64) else y.float()).contiguous()
+        table = _IndexCEFn.apply(y_pr.float(), y, True, self.activation != "logsoftmax", keep, None, -100)
+        return table[0] / float(y_pr.numel() // y_pr.shape[1])
+
+
+class RobustCrossEntropyLoss(Loss):
+    """metrics.py:511-521: nn.CrossEntropyLoss(weight, ignore_index, reduction, label_smoothing) on logits (B,K,H,W) against a label
+    map (B,1,H,W) or (B,H,W) of int64 / int32 / uint8 / fp32 / fp64 (truncated as ``.long()`` does; other dtypes are converted).
+    A Loss here (it composes with ``+``); the reference's is a bare nn.CrossEntropyLoss.  A label outside [0, K) that is not
+    ``ignore_index`` makes the value NaN and gets a zero gradient (torch asserts on the device)."""
+
+    def __init__(self, weight=None, ignore_index=-100, reduction="mean", label_smoothing=0.0, **kwargs):
+        super().__init__(**kwargs)
+        self.register_buffer("weight", None if weight is None else torch.as_tensor(weight, dtype=torch.float32).detach().clone().contiguous())
+        if self.weight is not None and self.weight.dim() != 1:
+            raise ValueError("RobustCrossEntropyLoss: weight is a vector of one value per class")
+        if not 0.0 <= float(label_smoothing) <= 1.0:
+            raise ValueError(f"RobustCrossEntropyLoss: label_smoothing must be inside [0, 1], got {label_smoothing}")
+        self.reduction = _check_reduction("RobustCrossEntropyLoss", reduction)
+        self.ignore_index, self.label_smoothing = int(ignore_index), float(label_smoothing)
+
+    def forward(self, y_pr, y_gt):
+        _check_device("RobustCrossEntropyLoss", y_pr, y_gt)
+        _check_index_input("RobustCrossEntropyLoss", y_pr)
+        B, K, H, W = y_pr.shape
+        if y_gt.dim() == 4 and y_gt.shape[1] == 1:
+            y_gt = y_gt[:, 0]
+        if y_gt.shape != (B, H, W):
+            raise NotImplementedError(f"RobustCrossEntropyLoss: a label map (B,1,H,W) or (B,H,W) for input {tuple(y_pr.shape)}, got {tuple(y_gt.shape)}")
+        if self.weight is not None and self.weight.shape[0] != K:
+            raise ValueError(f"RobustCrossEntropyLoss: {self.weight.shape[0]} class weights for {K} classes")
+        if self.weight is not None and self.weight.device != y_pr.device:
+            self.weight = self.weight.to(y_pr.device)
+        y = y_gt.detach()
+        y = (y if y.dtype in ops.ICE_LABEL_KINDS else y.long()).contiguous()
+        t = _IndexCEFn.apply(y_pr.float(), y, False, False, None, self.weight, self.ignore_index)
+        e = self.label_smoothing
+        if self.reduction == "mean":
+            return t[0] / t[1] if e == 0.0 else (1.0 - e) * t[0] / t[1] + (e / K) * t[2] / t[1]
+        return t[0] if e == 0.0 else (1.0 - e) * t[0] + (e / K) * t[2]

@@ -428,6 +428,83 @@ def seg_stats_bwd(logits, y, class_w, g_ce, g_tp, g_spr, dlogits):
          _p(_f32c(dlogits)), B, K, H, W, _stream())
 
 
+PWL_KINDS = {"l1": 0, "mse": 1, "bce": 2, "bce_with_logits": 3}       # CMU_PWL_* of the header
+PWL_MAX_C = 8
+
+
+def _pwl_args(kind, x, y, chan_w, chan_pw):
+    """(kind code, outer, C, inner) of the (outer, C, inner) view: C = 1 over the whole tensor without per-channel vectors, else the
+    vectors' length, which must be x.shape[1] unless it is 1."""
+    assert kind in PWL_KINDS, kind
+    assert y.shape == x.shape and y.is_cuda and y.is_contiguous() and y.dtype in (torch.float32, torch.float64)
+    assert chan_pw is None or kind == "bce_with_logits"
+    C = 1
+    for v in (chan_w, chan_pw):
+        if v is not None:
+            assert v.dim() == 1 and v.dtype == torch.float32 and v.is_contiguous() and 1 <= v.shape[0] <= PWL_MAX_C
+            assert C in (1, v.shape[0])
+            C = v.shape[0]
+    if C == 1:                               # no vectors, or one-element vectors: a factor on everything, whatever the shape
+        return PWL_KINDS[kind], 1, 1, x.numel()
+    assert x.dim() >= 2 and x.shape[1] == C and x.numel() > 0
+    return PWL_KINDS[kind], x.shape[0], C, x.numel() // (x.shape[0] * C)
+
+
+def pointwise_loss_fwd(kind, x, y, chan_w, chan_pw, out, ws):
+    """out[0] (fp64) = sum_i w_c term_i of fp32 ``x`` against fp32 / fp64 ``y`` for kind 'l1' / 'mse' / 'bce' / 'bce_with_logits';
+    chan_w / chan_pw: fp32 vectors over x.shape[1] or None (cmu_pointwise_loss_fwd)."""
+    k, outer, C, inner = _pwl_args(kind, x, y, chan_w, chan_pw)
+    assert out.dtype == torch.float64 and out.numel() == 1
+    call("cmu_pointwise_loss_fwd", k, _p(_f32c(x)), _p(y), int(y.dtype == torch.float64), _p(chan_w), _p(chan_pw), _p(out), outer, C, inner,
+         _p(ws), _stream())
+
+
+def pointwise_loss_bwd(kind, x, y, chan_w, chan_pw, g, dx):
+    """dx (fp32) = g[0] w_c dterm_i with ``g`` one fp64 value on the device (None = zero)."""
+    k, outer, C, inner = _pwl_args(kind, x, y, chan_w, chan_pw)
+    assert g is None or (g.dtype == torch.float64 and g.numel() == 1)
+    assert dx.shape == x.shape
+    call("cmu_pointwise_loss_bwd", k, _p(_f32c(x)), _p(y), int(y.dtype == torch.float64), _p(chan_w), _p(chan_pw), _p(g), _p(_f32c(dx)),
+         outer, C, inner, _stream())
+
+
+ICE_LABEL_KINDS = {torch.int64: 0, torch.int32: 1, torch.uint8: 2, torch.float32: 3, torch.float64: 4}    # CMU_ICE_LABEL_*
+ICE_ONEHOT_KINDS = {torch.float32: 5, torch.float64: 6}                                                      # CMU_ICE_ONEHOT_*
+
+
+def _ice_args(x, target, onehot, keep, class_w):
+    B, K, H, W = x.shape
+    assert 2 <= K <= SEG_MAX_K and target.is_cuda and target.is_contiguous()
+    if onehot:
+        assert target.shape == x.shape and target.dtype in ICE_ONEHOT_KINDS
+        kind = ICE_ONEHOT_KINDS[target.dtype]
+    else:
+        assert target.shape == (B, H, W) and target.dtype in ICE_LABEL_KINDS
+        kind = ICE_LABEL_KINDS[target.dtype]
+    keep = list(range(K)) if keep is None else list(keep)
+    assert keep and keep == sorted(set(keep)) and 0 <= keep[0] and keep[-1] < K
+    assert class_w is None or (class_w.shape == (K,) and class_w.dtype == torch.float32 and class_w.is_contiguous())
+    return B, K, H, W, kind, sum(1 << c for c in keep)
+
+
+def index_ce_fwd(x, target, onehot, log_input, keep, class_w, ignore_index, table, ws):
+    """table (3 fp64) = [sum w_t (-log p_t) | sum w_t | sum_kept w_c (-log p_c)] of (B,K,H,W) fp32 logits (``log_input``: log-
+    probabilities) against a (B,H,W) label plane, or (``onehot``) K planes whose arg-max over ``keep`` is the label (cmu_index_ce_fwd)."""
+    B, K, H, W, kind, mask = _ice_args(x, target, onehot, keep, class_w)
+    assert table.dtype == torch.float64 and table.numel() == 3 and table.is_contiguous()
+    call("cmu_index_ce_fwd", _p(_f32c(x)), _p(target), kind, int(bool(log_input)), mask, _p(class_w), int(ignore_index), _p(table),
+         B, K, H, W, _p(ws), _stream())
+
+
+def index_ce_bwd(x, target, onehot, log_input, keep, class_w, ignore_index, g, dx):
+    """dx (fp32) from the device-resident fp64 gradients g = (d/d table[0], d/d table[2]); None = zeros."""
+    B, K, H, W, kind, mask = _ice_args(x, target, onehot, keep, class_w)
+    assert g is None or (g.dtype == torch.float64 and g.numel() == 2 and g.is_contiguous())
+    assert dx.shape == x.shape
+    call("cmu_index_ce_bwd", _p(_f32c(x)), _p(target), kind, int(bool(log_input)), mask, _p(class_w), int(ignore_index), _p(g),
+         _p(_f32c(dx)), B, K, H, W, _stream())
+
+
 def infonce_inbatch_fwd_bwd(pred, keys, loss, dpred, rank, temperature, ct_weight):
     B, D = pred.shape
     call("cmu_infonce_inbatch_fwd_bwd", _p(_f32c(pred)), _p(_f32c(keys)), _p(loss), _p(dpred), B, keys.shape[0], D,

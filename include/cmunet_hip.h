@@ -295,6 +295,66 @@ int cmu_seg_stats_fwd(const float* logits, const void* y, int y_is_f64, const fl
 int cmu_seg_stats_bwd(const float* logits, const void* y, int y_is_f64, const float* class_w, const double* g_ce,
                       const double* g_tp, const double* g_spr, float* dlogits, int B, int K, int H, int W, void* stream);
 
+/* Element-wise losses of metrics.py:495-551 (nn.L1Loss / MSELoss / BCELoss / BCEWithLogitsLoss) as ONE streaming pass each way, with
+ * the conventions of cmu_seg_stats_fwd / _bwd: x fp32, y fp64 if y_is_f64 else fp32, per-lane fp64 accumulation -> block partials in
+ * ws -> a fixed-order finalisation (no floating-point atomics: the same bits every call), grid-stride loops under a block cap, 64-bit
+ * indexing, no host synchronisation.  The tensor is viewed as (outer, C, inner), 1 <= C <= CMU_PWL_MAX_C; the optional per-channel
+ * fp32 vectors chan_w[C] (a factor on the term) and chan_pw[C] (BCE_WITH_LOGITS's pos_weight; any other kind: CMU_ERR_ARG) are
+ * indexed by (i / inner) % C, NULL = ones.  The forward writes out[0] = S = sum_i w_c term_i, the backward
+ * dx_i = (float)(g[0] w_c dterm_i) with g one double read from DEVICE memory (NULL = zero); the caller applies 1/N for 'mean' as an
+ * op on the device scalar, so that autograd hands it back in g.  With c = 1 + (pw_c - 1) y:
+ *   kind                      term                                                      dterm
+ *   CMU_PWL_L1                |x - y|                                                   sign(x - y), 0 at ties
+ *   CMU_PWL_MSE               (x - y)^2                                                 2 (x - y)
+ *   CMU_PWL_BCE               -[y max(log x, -100) + (1 - y) max(log(1 - x), -100)]      (x - y) / max(x (1 - x), 1e-12)
+ *   CMU_PWL_BCE_WITH_LOGITS   (1 - y) x + c (log1p(e^-|x|) + max(-x, 0))                (1 - y) - c sigmoid(-x)
+ * (torch's own clamps).  A BCE prediction outside [0, 1] gives a NaN sum, not an error (raising would need a host sync).  The
+ * transcendental of a term is taken in fp32 on the fp32 prediction in a form that keeps its relative precision where it is tiny
+ * (log1p(-x), e^-|x| / (1 + e^-|x|)); its combination with y, the weights and g runs in fp64, without cancellation for 0 <= y <= 1.
+ * The access width is chosen for the WHOLE tensor: a lane takes 4 consecutive elements (16-byte accesses) when inner % 4 == 0 -- so
+ * that the 4 share a channel -- and x, y (and dx, backward) are 16-byte aligned, one element otherwise.
+ * ws: cmu_pointwise_loss_ws_bytes() bytes.                                                                                        */
+#define CMU_PWL_L1 0
+#define CMU_PWL_MSE 1
+#define CMU_PWL_BCE 2
+#define CMU_PWL_BCE_WITH_LOGITS 3
+#define CMU_PWL_MAX_C 8
+int64_t cmu_pointwise_loss_ws_bytes(void);
+int cmu_pointwise_loss_fwd(int kind, const float* x, const void* y, int y_is_f64, const float* chan_w, const float* chan_pw,
+                           double* out, int64_t outer, int C, int64_t inner, void* ws, void* stream);
+int cmu_pointwise_loss_bwd(int kind, const float* x, const void* y, int y_is_f64, const float* chan_w, const float* chan_pw,
+                           const double* g, float* dx, int64_t outer, int C, int64_t inner, void* stream);
+
+/* Cross entropy / negative log-likelihood with CLASS-INDEX targets (nn.CrossEntropyLoss / nn.NLLLoss under metrics.py:511-543) of
+ * x (B,K,H,W) fp32, 2 <= K <= 8, same conventions.  target_kind names what ``target`` holds:
+ *   CMU_ICE_LABEL_*   one label plane (B,H,W) of int64 / int32 / uint8 / fp32 / fp64, truncated to an integer as .long() does
+ *   CMU_ICE_ONEHOT_*  K planes (B,K,H,W) of fp32 / fp64; the label is the arg-max over the channels of keep_mask (bit c = channel c;
+ *                     the first maximum wins, an all-zero pixel gives the first kept channel, as torch.argmax does)
+ * x holds logits -- log p = log_softmax over ALL K channels, taken here -- or, with log_input != 0, log-probabilities used as they
+ * are.  keep_mask (label targets: pass (1 << K) - 1) also selects the channels of the third sum.  class_w: K fp32 weights, NULL = ones.
+ * A pixel whose label equals ignore_index adds nothing.  The forward writes table[3] doubles over the other pixels:
+ *   table[0] = sum w_t (-log p_t)      table[1] = sum w_t      table[2] = sum over kept c of w_c (-log p_c)
+ * from which torch's reductions follow on the device, with label smoothing e:  'mean' = (1 - e) T0 / T1 + (e / K) T2 / T1  (NaN when
+ * every pixel is ignored, as in torch),  'sum' = (1 - e) T0 + (e / K) T2.  The backward takes g[2] = (d/dT0, d/dT2) from DEVICE memory
+ * (NULL = zeros) and writes dx (B,K,H,W) fp32: g0 w_t (p_j - [j == t]) + g2 (p_j sum_kept w_c - [j kept] w_j) for logits,
+ * -g0 w_t [j == t] - g2 [j kept] w_j for log_input; zeros at ignored pixels.
+ * A label outside [0, K) that is not ignore_index is never used as an index: that pixel adds NaN to table[0] and gets a zero gradient
+ * (torch asserts on the device there).  -log p_c = (max - l_c) + log1p(sum of the other e^(l - max)), the difference in fp64: a
+ * confident pixel's tiny loss keeps its relative precision.  Pixels per lane: 4 (K <= 4) or 2 (K > 4) when H*W is a multiple of
+ * that and x, target (and dx, backward) are 16-byte aligned, else 1 -- for the whole tensor.  ws: cmu_index_ce_ws_bytes() bytes.     */
+#define CMU_ICE_LABEL_I64 0
+#define CMU_ICE_LABEL_I32 1
+#define CMU_ICE_LABEL_U8 2
+#define CMU_ICE_LABEL_F32 3
+#define CMU_ICE_LABEL_F64 4
+#define CMU_ICE_ONEHOT_F32 5
+#define CMU_ICE_ONEHOT_F64 6
+int64_t cmu_index_ce_ws_bytes(void);
+int cmu_index_ce_fwd(const float* x, const void* target, int target_kind, int log_input, int keep_mask, const float* class_w,
+                     int64_t ignore_index, double* table, int B, int K, int H, int W, void* ws, void* stream);
+int cmu_index_ce_bwd(const float* x, const void* target, int target_kind, int log_input, int keep_mask, const float* class_w,
+                     int64_t ignore_index, const double* g, float* dx, int B, int K, int H, int W, void* stream);
+
 /* CM-UNet in-batch InfoNCE (cmunet_head.py:72-88): pred (B,D) raw predictor output (L2-normalised inside),
  * keys (N,D) gathered, already normalised target projections; label i + B*rank; loss = ct_w*2*t*CE.
  * dpred (nullable) = d loss / d pred (B,D).  loss: 1 + B floats (loss[0] total, loss[1+b] per-row terms).     */
