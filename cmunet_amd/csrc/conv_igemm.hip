@@ -757,7 +757,8 @@ extern "C" int cmu_conv3x3_fwd_rows(const void* x, int64_t ldx, const void* wpac
 }
 
 // rows[r] = dense pixel index (b*H + y)*W + x of the r-th active pixel, patch-major (patch order = cmu_sparse_tile_list with tiles
-// of one patch; pixels row-major inside a patch); entries past the end up to `capacity` are -1; count[0] = number of rows
+// of one patch; pixels row-major inside a patch); entries past the end up to `capacity` are -1; count[0] = number of rows WRITTEN:
+// min(active pixels, capacity) -- a capacity below the number of active pixels keeps the first `capacity` rows
 __global__ void sparse_pixel_rows_kernel(const int* __restrict__ plist, const int* __restrict__ pcount, int f, int s, int H, int W,
                                          int* __restrict__ rows, int64_t capacity, int* __restrict__ count) {
     const int np = pcount[0];
@@ -772,7 +773,9 @@ __global__ void sparse_pixel_rows_kernel(const int* __restrict__ plist, const in
         }
         rows[r] = v;
     }
-    if (blockIdx.x == 0 && threadIdx.x == 0) count[0] = (int)n;
+    // (never more rows than the list holds, as sparse_pixel_rows_multi_kernel below: cmu_rows_channel_stats and cmu_bn_bwd_reduce_rows
+    // loop to *n_rows and never see the capacity)
+    if (blockIdx.x == 0 && threadIdx.x == 0) count[0] = (int)(n < capacity ? n : capacity);
 }
 extern "C" int64_t cmu_sparse_pixel_list_ws_bytes(int B, int f) { return ((int64_t)B * f * f + 16) * (int64_t)sizeof(int); }
 extern "C" int cmu_sparse_pixel_list(const uint8_t* active, int f, int B, int H, int W, int* rows, int64_t capacity, int* count, void* ws,

@@ -1,7 +1,8 @@
-"""What the three exact GPU files (test_gpu_conv3x3_exact.py, test_gpu_convT_exact.py, test_gpu_wgrad_exact.py) share: guard-banded
-buffers, the kernel tag of the last launch, bit comparison, and the launchers' dispatch rules RESTATED from the C++ (conv_igemm3.inc,
-conv_igemm3p.inc, conv_igemm5.inc, conv_gemm.inc, conv_wgrad.hip) so that every case asserts the kernel and the template form it is
-named after.  The only comparison is ``torch.equal`` on the bits."""
+"""What the exact GPU files (test_gpu_conv3x3_exact.py, test_gpu_convT_exact.py, test_gpu_wgrad_exact.py, and for the SparK list forms
+test_gpu_conv_rows_exact.py, test_gpu_wgrad_tiles_exact.py) share: guard-banded buffers, the kernel tag of the last launch, bit
+comparison, and the launchers' dispatch rules RESTATED from the C++ (conv_igemm3.inc, conv_igemm3p.inc, conv_igemm5.inc, conv_gemm.inc,
+conv_gather.inc, conv_wgrad.hip) so that every case asserts the kernel and the template form it is named after.  The only comparison is
+``torch.equal`` on the bits."""
 import contextlib
 import ctypes
 
@@ -115,7 +116,7 @@ def seam_pixels(B, H, W):
 DEFAULTS = {"CONV_NARROW": 1, "CONV_SLIM": 1, "CONV_PERSIST_PART": 1, "CONV_V5": 1, "CONV_PERSIST": 1, "CONV_WRES": 1, "CONV_WIDE": 1,
             "CONV_V6": 0, "V5_MIN_K": 128, "V5_MIN_K_BST": 256, "CONVT_SMALL": 1, "CONVT_GEMM": 1, "CONVT_SMALL_STEPS": 4,
             "WGRAD_WIDE": 1, "WGRAD_SWAP": 1, "WGRAD_SQUARE": 1, "WGRAD_WIDE_F32": 1, "WGT2_NX256": 1, "WGR_VEC": 1,
-            "WGRAD_BLOCKS1": 512, "WGRAD_BLOCKS": 256}
+            "WGRAD_BLOCKS1": 512, "WGRAD_BLOCKS": 256, "GATHER_NB": 0, "SPARK_GATHER": 1}
 ES = {"f32": 4, "f16": 2, "bf16": 2}
 _LIBRARY_KNOBS = {}
 
@@ -237,6 +238,47 @@ def wgrad3_rule(case, dt, base=None):
     return kernel, dict(form, splits=cls), splits, ntiles
 
 
+def gather_rule(case, dt, cus, capacity, base=None):
+    """cmu_conv3x3_rows_supported + launch_conv_gather (conv_gather.inc): -> (kernel tag, form: NB, the channels per workgroup, and the
+    grid).  256 channels per workgroup where N allows and the 256-channel grid -- ceil(capacity / 256) row tiles x N / 256 -- fills the
+    CUs; CMU_GATHER_NB = 128 | 256 forces a form."""
+    B, H, W, K, N = case["shape"]
+    kn = knob_values(case, base)
+    assert kn["SPARK_GATHER"] and N % 128 == 0 and K % (128 // ES[dt]) == 0, "not a shape of the gather kernel"
+    wide = N % 256 == 0
+    if wide and kn["GATHER_NB"] == 0:
+        wide = cdiv(capacity, 256) * (N // 256) >= cus
+    if kn["GATHER_NB"] == 128:
+        wide = False
+    nb = 256 if wide else 128
+    return "conv_gather_kernel", {"NB": nb, "grid": cdiv(capacity, 256) * (N // nb), "steps": K // (128 // ES[dt])}
+
+
+def wgrad3_tiles_rule(case, dt, base=None):
+    """cmu_conv3x3_wgrad_tiles: the list's tile height names the kernel -- 16: the first kernel, any shape; 8: the 64 x 64 form where it
+    serves the shape, else the wide kernel (never swapped) -> (kernel tag, form, splits, dense tile count).  The splits are the dense
+    launch's (wg_geometry / wg2_geometry / wg2s_geometry), whatever the list's count."""
+    B, H, W, CB, CA = case["shape"]
+    kn = knob_values(case, base)
+    assert kn["WGRAD_BLOCKS"] >= 8 and kn["WGRAD_BLOCKS1"] >= 8, "a value below the table's floor (8) falls back to the default"
+    es = ES[dt]
+    th = case["tiles"]["th"]
+    wide = bool(kn["WGRAD_WIDE"]) and es == 2 and CA % 128 == 0 and CB % 64 == 0
+    swap = bool(kn["WGRAD_WIDE"]) and bool(kn["WGRAD_SWAP"]) and es == 2 and CA == 64 and CB % 128 == 0
+    square = bool(kn["WGRAD_WIDE"]) and bool(kn["WGRAD_SQUARE"]) and es == 2 and CA % 64 == 0 and CB % 64 == 0 and not wide and not swap
+    if th == 8 and square:
+        kernel, nbase, aim = "conv_wgrad2s_kernel", (CA // 64) * (CB // 64), kn["WGRAD_BLOCKS"]
+    elif th == 8:
+        assert wide, "an 8 x 16 list needs a shape of the wide kernel"
+        kernel, nbase, aim = "conv_wgrad2_kernel", (CA // 128) * (CB // 64), kn["WGRAD_BLOCKS"]
+    else:
+        cw = 128 // es
+        kernel, nbase, aim = "conv_wgrad_kernel", cdiv(CA, cw) * cdiv(CB, cw), kn["WGRAD_BLOCKS1"]
+    ntiles = B * cdiv(W, 16) * cdiv(H, th)
+    splits = split_class(aim // nbase, ntiles)[0]
+    return kernel, {"splits": splits}, splits, ntiles
+
+
 def wgradT_rule(case, dt, base=None):
     """cmu_convT2x2_wgrad: CA = Cout, CB = Cin -> (kernel tag, form, splits, K tiles)."""
     B, H, W, CB, CA = case["shape"]
@@ -299,7 +341,7 @@ def wgradT_ws_bytes(case, dt, base=None):
 def slab_bytes(case, dt, kernel, splits):
     """Bytes of split-K slabs the kernel that runs writes: what ties the restated split count to the library's workspace size."""
     B, H, W, CB, CA = case["shape"]
-    taps = 9 if case["fam"] == "wg3" else 4
+    taps = 9 if case["fam"] in ("wg3", "wg3tiles") else 4
     if kernel == "conv_wgrad_kernel":
         cw = 128 // ES[dt]
         return splits * taps * cdiv(CA, cw) * cw * cdiv(CB, cw) * cw * 4

@@ -253,6 +253,13 @@ def assert_exact_caps(ref, dt="f32", stats=False):
 # One dict per case.  Keys:
 #   fam     c3f (cmu_conv3x3_fwd) | c3dg (cmu_conv3x3_dgrad_bn, flipped pack) | ctf (cmu_convT2x2_fwd) | ctdg (cmu_convT2x2_dgrad)
 #           | ctdgbn (cmu_convT2x2_dgrad_bn) | wg3 (cmu_conv3x3_wgrad) | wgt (cmu_convT2x2_wgrad)
+#           | c3rows (cmu_conv3x3_fwd_rows: the convolution read at a list of pixels) | wg3tiles (cmu_conv3x3_wgrad_tiles: the weight
+#           gradient of dY restricted to a list of tiles)
+#   rows    c3rows: the pixel list (``rows_list``) -- count (a number, or "all": every pixel of the batch), cap ("tight": the count
+#           rounded up to 256 | "slack": three more row tiles | "cus": 256 rows per CU of the device), flip (the transpose_flip pack: the
+#           data gradient the encoder runs), plist ((f, keep): the list comes from ops.PixelList on a patch map instead)
+#   tiles   wg3tiles: the tile list (``tiles_list``) -- th (8 | 16: tiles of th x 16 pixels), cls (the count relative to the split count:
+#           zero | below | equal | multiple | remainder | all), order (asc | perm), builder ((f, keep): the list comes from ops.TileList)
 #   shape   (B, H, W, K, N): K channels of the operand that is read, N channels written (c3dg / ctdg*: K = dY's, N = dX's; weight
 #           gradients: K = Cin, N = Cout).  ConvTranspose: H x W is the LOW resolution.
 #   dts     storage types;  rng  operand range of x / dY (and of the weights);  tf  None | relu_from of the pending transform
@@ -268,13 +275,22 @@ def assert_exact_caps(ref, dt="f32", stats=False):
 #   lift    f16 only: the weights of every eighth channel of the contraction are multiplied by this power of two (outputs past 2048:
 #           exact ties in f16, which holds every integer below that)
 def _c(fam, name, shape, kernel, dts=("f16", "bf16"), rng=(-3, 3), tf=None, stats=False, xs=0, ys=0, knobs=None, form=None, lift=0,
-       bias=0, wrng=None, spike=0):
-    return {"spike": spike, "wrng": tuple(wrng or rng), "fam": fam, "id": name, "shape": shape, "kernel": kernel, "dts": dts, "rng": rng, "tf": tf, "stats": stats, "xs": xs,
+       bias=0, wrng=None, spike=0, rows=None, tiles=None):
+    return {"rows": rows, "tiles": tiles, "spike": spike, "wrng": tuple(wrng or rng), "fam": fam, "id": name, "shape": shape, "kernel": kernel, "dts": dts, "rng": rng, "tf": tf, "stats": stats, "xs": xs,
             "ys": ys, "knobs": dict(knobs or {}), "form": dict(form or {}), "lift": lift, "bias": bias}
 
 
 ALL = ("f32", "f16", "bf16")
 H16 = ("f16", "bf16")
+# wg3tiles: (count class, list order) pairs -- every class in both orders where it matters, and a shorter walk for the second shape of a kernel
+_EVERY = (("zero", "asc"), ("below", "perm"), ("equal", "asc"), ("multiple", "perm"), ("remainder", "perm"), ("remainder", "asc"), ("all", "asc"))
+_FEW = (("zero", "asc"), ("below", "asc"), ("equal", "perm"), ("remainder", "perm"), ("all", "asc"))
+
+
+def _tile_cases(name, shape, kernel, dts, tf, th, knobs, splits, classes, xs=0, ys=0):
+    """One wg3tiles case per (count class, list order): the knob gives the launch ``splits`` splits, which the classes are relative to."""
+    return [_c("wg3tiles", f"{name} {cls} {order}", shape, kernel, dts, tf=tf, knobs=knobs, xs=xs, ys=ys,
+               tiles={"th": th, "cls": cls, "order": order}, form={"splits": splits}) for cls, order in classes]
 NN = {"CONV_NARROW": 0}      # keep the 128-channel blocks whatever the CU count (the narrow form is bit-identical and has its own case)
 
 CASES = [
@@ -398,13 +414,205 @@ CASES = [
     _c("wgt", "T f32 128->64 5x9", (1, 5, 9, 128, 64), "conv_wgradT2f_kernel", ("f32",), tf=64, ys=64, form={"splits": "clamped"}),
     _c("wgt", "T f32 256->128 7x33 short", (2, 7, 33, 256, 128), "conv_wgradT2f_kernel", ("f32",), knobs={"WGRAD_BLOCKS": 20},
        form={"splits": "short"}),
+    # ---- conv_gather_kernel: the convolution at a hand-built list of pixels (K = Cin: 1, 2, 3 steps of 128 bytes per tap) ---------------
+    #      grid = ceil(capacity / 256) * (N / NB): 1, 3, 8, 9, 17 (+ 2, 4, 5 and one workgroup per CU)
+    _c("c3rows", "rows 1 step ->128 count 255 grid 1", (2, 12, 13, 64, 128), "conv_gather_kernel", H16, xs=8, ys=16, lift=64,
+       rows={"count": 255, "cap": "tight"}, form={"NB": 128, "grid": 1}),
+    _c("c3rows", "rows f32 1 step ->128 count 255 grid 1", (2, 12, 13, 32, 128), "conv_gather_kernel", ("f32",), xs=8, ys=16,
+       rows={"count": 255, "cap": "tight"}, form={"NB": 128, "grid": 1}),
+    _c("c3rows", "rows 2 steps ->384 count 256 grid 3", (1, 17, 16, 128, 384), "conv_gather_kernel", H16, ys=128, lift=32,
+       rows={"count": 256, "cap": "tight"}, form={"NB": 128, "grid": 3}),
+    _c("c3rows", "rows f32 2 steps ->384 count 256 grid 3", (1, 17, 16, 64, 384), "conv_gather_kernel", ("f32",), ys=128,
+       rows={"count": 256, "cap": "tight"}, form={"NB": 128, "grid": 3}),
+    _c("c3rows", "rows 3 steps ->256 NB 128 count 1 grid 8", (1, 3, 5, 192, 256), "conv_gather_kernel", H16, xs=64, lift=32,
+       knobs={"GATHER_NB": 128}, rows={"count": 1, "cap": "slack"}, form={"NB": 128, "grid": 8}),
+    _c("c3rows", "rows f32 3 steps ->256 NB 128 count 1 grid 8", (1, 3, 5, 96, 256), "conv_gather_kernel", ("f32",), xs=32,
+       knobs={"GATHER_NB": 128}, rows={"count": 1, "cap": "slack"}, form={"NB": 128, "grid": 8}),
+    _c("c3rows", "rows 1 step ->256 NB 256 count 0", (1, 4, 4, 64, 256), "conv_gather_kernel", H16, ys=8,
+       knobs={"GATHER_NB": 256}, rows={"count": 0, "cap": "tight"}, form={"NB": 256, "grid": 1}),
+    _c("c3rows", "rows 2 steps ->256 NB 256 count 257 grid 5", (2, 12, 13, 128, 256), "conv_gather_kernel", H16, xs=16, ys=256, lift=32,
+       knobs={"GATHER_NB": 256}, rows={"count": 257, "cap": "slack"}, form={"NB": 256, "grid": 5}),
+    _c("c3rows", "rows f32 1 step ->256 NB 256 count 257 grid 5", (2, 12, 13, 32, 256), "conv_gather_kernel", ("f32",), ys=256,
+       knobs={"GATHER_NB": 256}, rows={"count": 257, "cap": "slack"}, form={"NB": 256, "grid": 5}),
+    _c("c3rows", "rows 3 steps ->384 count 700 grid 9", (3, 16, 15, 192, 384), "conv_gather_kernel", H16, rng=(-2, 2),
+       rows={"count": 700, "cap": "tight"}, form={"NB": 128, "grid": 9}),
+    _c("c3rows", "rows 1 step ->128 count 3518 grid 17", (3, 33, 37, 64, 128), "conv_gather_kernel", H16,
+       rows={"count": 3518, "cap": "slack"}, form={"NB": 128, "grid": 17}),
+    _c("c3rows", "rows ->256 no knob, few row tiles: NB 128 grid 4", (1, 16, 19, 64, 256), "conv_gather_kernel", H16,
+       rows={"count": 300, "cap": "tight"}, form={"NB": 128, "grid": 4}),
+    _c("c3rows", "rows ->256 no knob, a row tile per CU: NB 256", (1, 16, 19, 64, 256), "conv_gather_kernel", H16, lift=64,
+       rows={"count": 300, "cap": "cus"}, form={"NB": 256}),
+    _c("c3rows", "rows every pixel of 3 x 5 x 11, flipped pack", (3, 5, 11, 128, 256), "conv_gather_kernel", ALL, xs=32, ys=32, lift=32,
+       knobs={"GATHER_NB": 256}, rows={"count": "all", "cap": "tight", "flip": True}, form={"NB": 256, "grid": 1}),
+    _c("c3rows", "rows every pixel of 3 x 9 x 7, flipped pack", (3, 9, 7, 64, 128), "conv_gather_kernel", ALL, lift=64,
+       rows={"count": "all", "cap": "tight", "flip": True}, form={"NB": 128, "grid": 1}),
+    _c("c3rows", "rows builder list 2 x 8 x 8, patches of 2 px", (2, 8, 8, 64, 128), "conv_gather_kernel", ALL,
+       rows={"plist": (4, 5), "cap": "tight"}, form={"NB": 128, "grid": 1}),
+    _c("c3rows", "rows builder list 3 x 16 x 16, patches of 1 px, flipped", (3, 16, 16, 128, 128), "conv_gather_kernel", H16, lift=32,
+       rows={"plist": (16, 100), "cap": "tight", "flip": True}, form={"NB": 128, "grid": 2}),
+    # ---- cmu_conv3x3_wgrad_tiles: the three kernels over 16 x 16 and 8 x 16 tile lists, counts relative to the split count -------------
+    *_tile_cases("tiles first 72->40 2x20x40", (2, 20, 40, 72, 40), "conv_wgrad_kernel", H16, -32, 16, {"WGRAD_BLOCKS1": 8}, 4, _EVERY, xs=8, ys=8),
+    *_tile_cases("tiles first f32 72->40 2x20x40", (2, 20, 40, 72, 40), "conv_wgrad_kernel", ("f32",), -32, 16, {"WGRAD_BLOCKS1": 24}, 4, _FEW, xs=4),
+    *_tile_cases("tiles first f32 64->128 2x20x40", (2, 20, 40, 64, 128), "conv_wgrad_kernel", ("f32",), 32, 16, {"WGRAD_BLOCKS1": 32}, 4, _FEW),
+    *_tile_cases("tiles wide 64->128 3x20x40", (3, 20, 40, 64, 128), "conv_wgrad2_kernel", H16, 32, 8, {"WGRAD_BLOCKS": 8}, 8, _EVERY, ys=16),
+    *_tile_cases("tiles wide 128->256 1x20x40", (1, 20, 40, 128, 256), "conv_wgrad2_kernel", H16, -64, 8, {"WGRAD_BLOCKS": 16}, 4, _FEW, xs=16),
+    *_tile_cases("tiles square 64->64 3x20x40", (3, 20, 40, 64, 64), "conv_wgrad2s_kernel", H16, 8, 8, {"WGRAD_BLOCKS": 8}, 8, _EVERY, xs=16),
+    *_tile_cases("tiles square 192->64 2x20x40", (2, 20, 40, 192, 64), "conv_wgrad2s_kernel", H16, -64, 8, {"WGRAD_BLOCKS": 12}, 4, _FEW, ys=16),
+    _c("wg3tiles", "tiles first builder 2x32x32", (2, 32, 32, 72, 40), "conv_wgrad_kernel", ALL, tf=8, knobs={"WGRAD_BLOCKS1": 8},
+       tiles={"th": 16, "builder": (2, 3)}),
+    _c("wg3tiles", "tiles wide builder 3x64x64", (3, 64, 64, 64, 128), "conv_wgrad2_kernel", H16, tf=0, knobs={"WGRAD_BLOCKS": 8},
+       tiles={"th": 8, "builder": (8, 21)}),
+    _c("wg3tiles", "tiles square builder 3x64x64", (3, 64, 64, 64, 64), "conv_wgrad2s_kernel", H16, tf=-32, knobs={"WGRAD_BLOCKS": 8},
+       tiles={"th": 8, "builder": (4, 5)}),
 ]
 
 # every tag cmu_set_kernel_tag can set, apart from conv_igemm6_kernel (opt-in; pinned through its bit-identity test against the dense
-# launch) and conv_gather_kernel (the SparK row-list form, likewise)
+# launch).  conv_gather_kernel (the SparK row-list form) is a kernel of its own -- own addressing, K order, staging and scatter -- and has
+# its own exact cases (fam c3rows, tests/test_gpu_conv_rows_exact.py); the tile-list forms of the weight-gradient kernels share the dense
+# kernels' tags and have theirs in fam wg3tiles (tests/test_gpu_wgrad_tiles_exact.py).  Of the list forms only cmu_conv3x3_fwd_tiles is
+# pinned through identity with the dense launch (tests/test_gpu_sparse_tiles.py: torch.equal against it).
 PINNED_KERNELS = {"conv_igemm_kernel", "conv_igemm3_kernel", "conv_igemm3p_kernel", "conv_igemm5_kernel", "conv_gemm_kernel",
                   "conv_gemm_s_kernel", "conv_wgrad_kernel", "conv_wgrad2_kernel", "conv_wgrad2s_kernel", "conv_wgrad2f_kernel",
-                  "conv_wgradT2_kernel", "conv_wgradT2f_kernel"}
+                  "conv_wgradT2_kernel", "conv_wgradT2f_kernel", "conv_gather_kernel"}
+# every list-driven C entry of the convolution sources and the file that holds it to an independent reference
+LIST_ENTRIES = {"cmu_conv3x3_fwd_rows": "test_gpu_conv_rows_exact.py", "cmu_conv3x3_wgrad_tiles": "test_gpu_wgrad_tiles_exact.py",
+                "cmu_conv3x3_fwd_tiles": "test_gpu_sparse_tiles.py", "cmu_conv3x3_c1_fwd_tiles": "test_gpu_elem_fp64.py",
+                "cmu_conv3x3_c1_wgrad_bn_tiles": "test_gpu_elem_fp64.py", "cmu_sparse_tile_list": "test_gpu_sparse_lists.py",
+                "cmu_sparse_tile_lists": "test_gpu_sparse_lists.py", "cmu_sparse_pixel_list": "test_gpu_sparse_lists.py",
+                "cmu_sparse_pixel_lists": "test_gpu_sparse_lists.py"}
+
+
+# ------------------------------------------------------------------------------------------------
+# lists (c3rows, wg3tiles): built by hand, from the case alone
+# ------------------------------------------------------------------------------------------------
+ROW_TILE = 256     # rows of the list per workgroup of the gather kernel
+
+
+def patch_map(B, f, keep, seed):
+    """(B, f, f) uint8 patch map with ``keep`` active patches per image."""
+    g = torch.Generator().manual_seed(int(seed))
+    a = torch.zeros(B, f * f, dtype=torch.uint8)
+    for b in range(B):
+        a[b, torch.randperm(f * f, generator=g)[:keep]] = 1
+    return a.view(B, f, f)
+
+
+def pixel_list_of(active, H):
+    """What cmu_sparse_pixel_list(s) must write for a square level of side H = f * s: the pixels of the active patches, patches in
+    ascending (b, fy, fx) order, pixels row-major inside a patch.  Written out with loops (a second statement, no index algebra)."""
+    B, f = active.shape[0], active.shape[-1]
+    s = H // f
+    out = []
+    for b in range(B):
+        for fy in range(f):
+            for fx in range(f):
+                if int(active[b, fy, fx]):
+                    for py in range(s):
+                        for px in range(s):
+                            out.append((b * H + fy * s + py) * H + fx * s + px)
+    return torch.tensor(out, dtype=torch.int32)
+
+
+def rows_count(case):
+    """The list's count, from the case alone."""
+    B, H, W = case["shape"][:3]
+    r = case["rows"]
+    if "plist" in r:
+        return B * r["plist"][1] * (H // r["plist"][0]) ** 2
+    return B * H * W if r["count"] == "all" else int(r["count"])
+
+
+def rows_capacity(case, count, cus=256):
+    tight = max(ROW_TILE, -(-count // ROW_TILE) * ROW_TILE)
+    return {"tight": tight, "slack": tight + 3 * ROW_TILE, "cus": ROW_TILE * cus}[case["rows"]["cap"]]
+
+
+def rows_list(case, cus=256):
+    """-> (rows int32 (capacity,), count).  The first ``count`` entries are a fixed random permutation of distinct pixels of the
+    (B, H, W) batch; EVERY entry past the count is a valid pixel too, an unlisted one wherever the batch has one, so that a kernel
+    that reads past the count writes a pixel whose previous bits must survive, and never reads out of range."""
+    B, H, W = case["shape"][:3]
+    r = case["rows"]
+    npix = B * H * W
+    if "plist" in r:
+        f, keep = r["plist"]
+        assert H == W and H % f == 0
+        listed = pixel_list_of(patch_map(B, f, keep, case_seed(case) + 13), H).long()
+    else:
+        g = torch.Generator().manual_seed(case_seed(case) + 11)
+        perm = torch.randperm(npix, generator=g)
+        count = npix if r["count"] == "all" else int(r["count"])
+        assert count <= npix
+        listed = perm[:count]
+    count = len(listed)
+    on = torch.zeros(npix, dtype=torch.bool)
+    on[listed] = True
+    rest = (~on).nonzero()[:, 0]
+    if len(rest) == 0:
+        rest = torch.arange(npix)
+    cap = rows_capacity(case, count, cus)
+    pad = rest[torch.arange(cap - count) % len(rest)]
+    return torch.cat([listed, pad]).to(torch.int32), count
+
+
+def rows_expected(stored_y, rows, count, before):
+    """The buffer after cmu_conv3x3_fwd_rows: ``stored_y`` (B, H, W, N) at the pixels rows[:count], ``before`` everywhere else."""
+    N = stored_y.shape[-1]
+    out = before.clone().reshape(-1, N)
+    idx = rows[:count].long().to(out.device)
+    out[idx] = stored_y.reshape(-1, N)[idx]
+    return out.reshape(stored_y.shape)
+
+
+def layer_weight(w, flip):
+    """The tensor to hand to the packer so that the packed weight is ``w`` (N, K, 3, 3): ``w`` itself, or -- transpose_flip=True, the
+    data-gradient pack -- the LAYER's weight (K, N, 3, 3), whose flipped transpose is ``w``."""
+    return w.flip(2, 3).transpose(0, 1).contiguous() if flip else w
+
+
+def tiles_geometry(case):
+    B, H, W = case["shape"][:3]
+    th = case["tiles"]["th"]
+    return B, -(-H // th), -(-W // 16), th
+
+
+def tiles_count(case, splits, ntiles):
+    """The list count of a class, relative to the split count of the launch (split s walks the entries s, s + splits, ...)."""
+    cls = case["tiles"]["cls"]
+    assert splits >= 2 and 2 * splits < ntiles, "the case needs a split count between 2 and half the dense tile count"
+    rem = 2 * splits + splits // 2 if 2 * splits + splits // 2 < ntiles else splits + splits // 2
+    return {"zero": 0, "below": splits // 2, "equal": splits, "multiple": 2 * splits, "remainder": rem, "all": ntiles}[cls]
+
+
+def tiles_list(case, splits):
+    """-> (list int32 (dense tile count,), count): ``count`` distinct dense tile ids (b * tilesY + ty) * tilesX + tx, ascending or in a
+    fixed permutation; the entries past the count hold valid, unlisted tile ids (listed ones only when every tile is listed)."""
+    B, tY, tX, th = tiles_geometry(case)
+    nt = B * tY * tX
+    count = tiles_count(case, splits, nt)
+    g = torch.Generator().manual_seed(case_seed(case) + 12)
+    perm = torch.randperm(nt, generator=g)
+    listed = perm[:count]
+    if case["tiles"]["order"] == "asc":
+        listed = listed.sort().values
+    rest = perm[count:] if count < nt else perm
+    pad = rest[torch.arange(nt - count) % len(rest)]
+    return torch.cat([listed, pad]).to(torch.int32), count
+
+
+def tiles_mask(case, tlist, count):
+    """(B, H, W, 1) float64: 1 at the pixels of the tiles tlist[:count]."""
+    B, H, W = case["shape"][:3]
+    _, tY, tX, th = tiles_geometry(case)
+    on = torch.zeros(B * tY * tX, dtype=torch.float64)
+    on[tlist[:count].long().cpu()] = 1.0
+    m = on.view(B, tY, 1, tX, 1).expand(B, tY, th, tX, 16).reshape(B, tY * th, tX * 16)
+    return m[:, :H, :W].unsqueeze(-1).contiguous()
+
+
+def wgrad_tiles_exact(case, x, dy, tlist, count, transform=None):
+    """conv3x3_wgrad_exact of dY * [the pixel lies in a listed tile]: x is read wherever the halo of a listed tile reaches."""
+    return conv3x3_wgrad_exact(x, dy.double() * tiles_mask(case, tlist, count).to(dy.device), transform)
 
 
 # ------------------------------------------------------------------------------------------------
@@ -444,18 +652,20 @@ def weights_of(case, dt, seed):
     B, H, W, K, N = case["shape"]
     lo, hi = case["wrng"]
     fam = case["fam"]
-    shape = {"c3f": (N, K, 3, 3), "c3dg": (K, N, 3, 3), "ctf": (K, N, 2, 2), "ctdg": (N, K, 2, 2), "ctdgbn": (N, K, 2, 2)}[fam]
+    shape = {"c3f": (N, K, 3, 3), "c3rows": (N, K, 3, 3), "c3dg": (K, N, 3, 3), "ctf": (K, N, 2, 2), "ctdg": (N, K, 2, 2),
+             "ctdgbn": (N, K, 2, 2)}[fam]
     w = int_operands(shape, lo, hi, 1.0, seed + 3)
     if case["lift"] and dt == "f16":
-        if fam in ("c3f", "ctdg", "ctdgbn"):       # (the contraction runs over the weight's second dimension)
+        if fam in ("c3f", "c3rows", "ctdg", "ctdgbn"):       # (the contraction runs over the weight's second dimension)
             w[:, ::8] *= float(case["lift"])
         else:
             w[::8] *= float(case["lift"])
     return w
 
 
-def reference_of(case, dt, device="cpu"):
-    """Integer operands and the exact reference of one case -> (operands dict, reference dict)."""
+def reference_of(case, dt, device="cpu", splits=None):
+    """Integer operands and the exact reference of one case -> (operands dict, reference dict).  ``splits`` (wg3tiles): the split count of
+    the launch, which the list classes are relative to (the GPU file passes the restated rule's; default: the case's ``form``)."""
     B, H, W, K, N = case["shape"]
     lo, hi = case["rng"]
     fam, seed = case["fam"], case_seed(case)
@@ -497,6 +707,22 @@ def reference_of(case, dt, device="cpu"):
         o["dy"] = int_operands((B, H, W, N), lo, hi, 1.0, seed + 6).to(device)
         o["tf"] = make_transform(case, K, seed)
         ref = conv3x3_wgrad_exact(o["x"], o["dy"], o["tf"])
+    elif fam == "c3rows":
+        assert case["tf"] is None and not case["stats"]
+        o["x"] = int_operands((B, H, W, K), lo, hi, 1.0, seed).to(device)
+        o["w"] = weights_of(case, dt, seed)
+        if "plist" not in case["rows"]:        # (a builder-made list is read back from the device by the GPU file)
+            o["rows"], o["count"] = rows_list(case)
+        ref = conv3x3_exact(o["x"], o["w"], None, dt)
+    elif fam == "wg3tiles":
+        o["x"] = int_operands((B, H, W, K), lo, hi, 1.0, seed).to(device)
+        o["dy"] = int_operands((B, H, W, N), lo, hi, 1.0, seed + 6).to(device)      # non-zero in the unlisted tiles as well
+        o["tf"] = make_transform(case, K, seed)
+        if "builder" in case["tiles"]:
+            ref = conv3x3_wgrad_exact(o["x"], o["dy"], o["tf"])                     # (every tile: an upper bound of the list's terms)
+        else:
+            o["tiles"], o["count"] = tiles_list(case, splits or case["form"]["splits"])
+            ref = wgrad_tiles_exact(case, o["x"], o["dy"], o["tiles"], o["count"], o["tf"])
     elif fam == "wgt":
         o["x"] = int_operands((B, H, W, K), lo, hi, 1.0, seed).to(device)
         o["dout"] = int_operands((B, 2 * H, 2 * W, N), lo, hi, 1.0, seed + 6).to(device)

@@ -136,6 +136,65 @@ def test_convT2x2_forms_are_conv_transpose2d_and_its_gradients(exact, relu_from)
     assert torch.equal(slab, r["bstats"]) and slab.shape == (B * 1 * 1, 2, Cin)
 
 
+@pytest.mark.parametrize("exact", [True, False])
+def test_rows_reference_is_conv2d_at_the_listed_pixels_and_the_sentinel_elsewhere(exact):
+    """fam c3rows: the reference read at the listed pixels equals torch's float64 convolution there -- at every border, corner and image
+    seam of a non-square batch, in the list's own order -- and the buffer keeps what it held everywhere else; with the flipped pack the
+    packed weight is the flipped transpose of the layer's."""
+    case = next(c for c in R.CASES if c["id"] == "rows every pixel of 3 x 5 x 11, flipped pack")
+    part = dict(case, rows={"count": 100, "cap": "slack"})
+    for c in (case, part):
+        B, H, W, K, N = c["shape"]
+        x, w = operands((B, H, W, K), exact, 21), operands((N, K, 3, 3), exact, 22)
+        rows, count = R.rows_list(c)
+        assert rows.dtype == torch.int32 and len(rows) == R.rows_capacity(c, count) and len(rows) % 256 == 0
+        assert int(rows.min()) >= 0 and int(rows.max()) < B * H * W and len(set(rows[:count].tolist())) == count
+        r = R.conv3x3_exact(x, w, None, "f32")
+        before = torch.full((B, H, W, N), -1536.0, dtype=torch.float64)
+        got = R.rows_expected(r["y"], rows, count, before)
+        ref = nhwc(F.conv2d(nchw(x.double()), w.double(), padding=1))
+        listed = torch.zeros(B * H * W, dtype=torch.bool)
+        listed[rows[:count].long()] = True
+        listed = listed.view(B, H, W)
+        assert int(listed.sum()) == count and close(got[listed], ref[listed], exact)
+        assert bool((got[~listed] == -1536.0).all())
+        if count < B * H * W:                  # the entries past the count name unlisted pixels
+            assert not bool(listed.view(-1)[rows[count:].long()].any())
+        # the flipped pack: conv with w == the data gradient of the layer whose weight is layer_weight(w, True)
+        wl = R.layer_weight(w, True)
+        xin = torch.zeros(B, N, H, W, dtype=torch.float64, requires_grad=True)
+        (F.conv2d(xin, wl.double(), padding=1) * nchw(x.double())).sum().backward()
+        assert close(nhwc(xin.grad), ref, exact) and R.layer_weight(w, False) is w
+
+
+def test_pixel_list_of_is_the_patch_major_order():
+    act = torch.tensor([[[0, 1], [1, 0]]], dtype=torch.uint8)
+    assert R.pixel_list_of(act, 4).tolist() == [2, 3, 6, 7, 8, 9, 12, 13]
+
+
+@pytest.mark.parametrize("exact", [True, False])
+@pytest.mark.parametrize("th", [8, 16])
+def test_wgrad_tiles_reference_is_conv2d_weight_of_the_masked_gradient(exact, th):
+    """fam wg3tiles: dW of dY restricted to the listed tiles, against torch's float64 weight gradient of dY zeroed OUTSIDE them pixel by
+    pixel (a loop over tiles: a second statement of the dense tile numbering (b * tilesY + ty) * tilesX + tx, partial tiles included)."""
+    case = next(c for c in R.CASES if c["fam"] == "wg3tiles" and c["tiles"]["th"] == th and c["tiles"].get("cls") == "remainder"
+                and c["tiles"]["order"] == "perm")
+    B, H, W, K, N = case["shape"]
+    x, dy = operands((B, H, W, K), exact, 23), operands((B, H, W, N), exact, 24)
+    tf = transform(K, exact, 25, 8)
+    tl, count = R.tiles_list(case, 4)
+    tY, tX = -(-H // th), -(-W // 16)
+    assert len(tl) == B * tY * tX and 0 < count < len(tl) and len(set(tl[:count].tolist())) == count
+    assert not set(tl[:count].tolist()) & set(tl[count:].tolist())
+    d = torch.zeros(B, H, W, N, dtype=torch.float64)
+    for t in tl[:count].tolist():
+        b, ty, tx = t // (tY * tX), (t // tX) % tY, t % tX
+        d[b, ty * th:(ty + 1) * th, tx * 16:(tx + 1) * 16] = dy[b, ty * th:(ty + 1) * th, tx * 16:(tx + 1) * 16].double()
+    ref = torch.nn.grad.conv2d_weight(nchw(torch_transform(x, tf)), (N, K, 3, 3), nchw(d), padding=1)
+    assert close(R.wgrad_tiles_exact(case, x, dy, tl, count, tf)["dW"], ref, exact)
+    assert not close(R.conv3x3_wgrad_exact(x, dy, tf)["dW"], ref, exact)
+
+
 def test_rounding_report_counts_ties():
     y = torch.tensor([256.0, 257.0, 258.0, 259.0, 513.0, 514.0, 515.0, 2049.0, 2050.0, 4097.0, 4098.0])
     # bf16 keeps 8 bits: step 2 from 256 (257, 259 are ties), 4 from 512 (514 is one; 513, 515 are not), 16 from 2048, 32 from 4096
@@ -167,17 +226,17 @@ def test_every_case_keeps_every_fp32_sum_below_2_pow_24(case, dt):
 
 
 @pytest.mark.parametrize("dt,fams", [("f16", ("c3f",)), ("bf16", ("c3f",)), ("f16", ("ctf",)), ("bf16", ("ctf",)), ("bf16", ("c3dg",)),
-                                     ("bf16", ("ctdgbn",))])
+                                     ("bf16", ("ctdgbn",)), ("f16", ("c3rows",)), ("bf16", ("c3rows",))])
 def test_each_family_has_a_case_with_exact_ties(dt, fams):
     """Round-to-nearest-even is only told from other roundings on exact ties: each 16-bit type has them in a forward case of each
-    family (f16 through the power-of-two lift of every eighth input channel).  The data gradients have a bf16 case whose dX is inexact,
+    family (the row-list family c3rows included) (f16 through the power-of-two lift of every eighth input channel).  The data gradients have a bf16 case whose dX is inexact,
     so that sums taken on the unrounded dX differ (in f16 every integer dX of these cases is below 2048 and exact)."""
     ties = 0
     for c in R.CASES:
         if c["fam"] in fams and dt in c["dts"]:
             _, ref = R.reference_of(c, dt)
             rep = R.assert_exact_caps(ref, dt, c["stats"])
-            ties += rep["ties"] if fams[0] in ("c3f", "ctf") else int(rep["inexact"] > 0)
+            ties += rep["ties"] if fams[0] in ("c3f", "ctf", "c3rows") else int(rep["inexact"] > 0)
     assert ties > 0
 
 
@@ -185,7 +244,8 @@ def test_cases_name_every_pinned_kernel_and_are_unique():
     assert {c["kernel"] for c in R.CASES} == R.PINNED_KERNELS
     assert len({(c["fam"], c["id"]) for c in R.CASES}) == len(R.CASES)
     for c in R.CASES:
-        assert set(c["dts"]) <= {"f32", "f16", "bf16"} and c["fam"] in ("c3f", "c3dg", "ctf", "ctdg", "ctdgbn", "wg3", "wgt")
+        assert set(c["dts"]) <= {"f32", "f16", "bf16"} and c["fam"] in ("c3f", "c3dg", "ctf", "ctdg", "ctdgbn", "wg3", "wgt", "c3rows", "wg3tiles")
+        assert (c["rows"] is not None) == (c["fam"] == "c3rows") and (c["tiles"] is not None) == (c["fam"] == "wg3tiles")
         epc = 4 if "f32" in c["dts"] else 8
         assert all(v % epc == 0 for v in (c["xs"], c["ys"], c["shape"][3], c["shape"][4]))
         assert c["tf"] is None or c["tf"] % epc == 0
@@ -201,14 +261,21 @@ def test_the_restated_launcher_rules_give_each_case_its_kernel_on_256_cus(case, 
         kernel, form = G.conv3_rule(case, dt, 256, case["tf"] is not None, fam == "c3dg")
     elif fam in ("ctf", "ctdg", "ctdgbn"):
         kernel, form = G.convT_rule(case, dt, fam != "ctf", case["tf"] is not None)
+    elif fam == "c3rows":
+        kernel, form = G.gather_rule(case, dt, 256, R.rows_capacity(case, R.rows_count(case), 256))
+    elif fam == "wg3tiles":
+        kernel, form = G.wgrad3_tiles_rule(case, dt)[:2]
     else:
         kernel, form = (G.wgrad3_rule if fam == "wg3" else G.wgradT_rule)(case, dt)[:2]
     G.assert_form(case, dt, kernel, form)
 
 
-def test_pinned_kernels_are_every_tag_of_the_library_but_two():
-    """Every tag ``cmu_set_kernel_tag`` can set (read from the sources), apart from conv_igemm6_kernel and conv_gather_kernel, is asserted by
-    a case: a new kernel tag, or a case list that loses one, fails here."""
+def test_pinned_kernels_are_every_tag_of_the_library_but_one():
+    """Every tag ``cmu_set_kernel_tag`` can set (read from the sources), apart from conv_igemm6_kernel, is asserted by a case: a new kernel
+    tag, or a case list that loses one, fails here.  Per source file: every C entry of the convolution sources that takes a device-side
+    list (a ``tile_list`` / ``rows`` / ``lists`` argument) is named in ``LIST_ENTRIES`` with the test file that holds it to an independent
+    reference, that file exists and calls it, and every kernel that reads ``p.tile_list`` belongs to a pinned tag: a new gather or list
+    form cannot go untested."""
     import glob
     import os
     import re
@@ -217,8 +284,31 @@ def test_pinned_kernels_are_every_tag_of_the_library_but_two():
     for path in glob.glob(os.path.join(csrc, "*")):
         with open(path, errors="replace") as f:
             tags |= set(re.findall(r'cmu_set_kernel_tag\("([a-zA-Z0-9_]+)"\)', f.read()))
-    assert tags - {"conv_igemm6_kernel", "conv_gather_kernel"} == R.PINNED_KERNELS
+    assert tags - {"conv_igemm6_kernel"} == R.PINNED_KERNELS
     assert {c["kernel"] for c in R.CASES} == R.PINNED_KERNELS
+    tests = os.path.dirname(os.path.abspath(__file__))
+    entries, readers = set(), set()
+    for path in glob.glob(os.path.join(csrc, "*")):
+        with open(path, errors="replace") as f:
+            text = f.read()
+        # extern "C" entries of the convolution and list sources with a device-side list among their arguments
+        for name, args in re.findall(r'extern "C" int (cmu_(?:conv3x3|sparse)_[a-z0-9_]+)\((.*?)\)\s*\{', text, re.S):
+            if re.search(r"\*\s*(const\*\s*)?(tile_list|rows|list|lists)\b", args):
+                entries.add(name)
+        if "p.tile_list" in text:
+            readers.add(os.path.basename(path))
+    assert entries == set(R.LIST_ENTRIES), sorted(entries ^ set(R.LIST_ENTRIES))
+    for entry, fname in R.LIST_ENTRIES.items():
+        with open(os.path.join(tests, fname)) as f:
+            text = f.read()
+        called = entry[4:] in text or {"cmu_sparse_tile_list": "TileList(", "cmu_sparse_tile_lists": "build_lists(", "cmu_sparse_pixel_list": "PixelList(",
+                                       "cmu_sparse_pixel_lists": "build_lists("}.get(entry, entry) in text
+        assert called, f"{fname} does not call {entry}"
+    # the sources whose kernels walk a list: each has cases of the list families
+    assert readers == {"conv_gather.inc", "conv_igemm.hip", "conv_igemm3p.inc", "conv_igemm5.inc", "conv_igemm6.inc", "conv_wgrad.hip",
+                       "conv_wgrad2.inc", "conv_wgrad2s.inc"}, f"a new source reads a device-side list: give it exact cases ({sorted(readers)})"
+    assert {c["kernel"] for c in R.CASES if c["fam"] == "c3rows"} == {"conv_gather_kernel"}
+    assert {c["kernel"] for c in R.CASES if c["fam"] == "wg3tiles"} == {"conv_wgrad_kernel", "conv_wgrad2_kernel", "conv_wgrad2s_kernel"}
 
 
 @pytest.mark.parametrize("dt", ["f16", "bf16"])

@@ -20,7 +20,8 @@ Stored intermediate gradients (the pool's dA, the head's dX) enter the reference
 
 Not covered (they need tens of GB): the 2^20-workgroup cap of bn_bwd_apply / conv1x1_head_bn_apply / the uncapped max-pool apply,
 and every ``> 2^31`` index branch (cmu_pixel_coords' 64-bit divisions, the head kernels' 64-bit (image, pixel) split).  The
-cells forms and the conv kernels' fused BatchNorm epilogues stay with their own tests.  NaN / inf inputs are out of scope: the
+cells forms and the conv kernels' fused BatchNorm epilogues stay with their own tests.  The first layer over its tile list
+(cmu_conv3x3_c1_fwd_tiles, cmu_conv3x3_c1_wgrad_bn_tiles) is held to the same references restricted to the listed tiles.  NaN / inf inputs are out of scope: the
 kernels' fmaxf squashes a NaN activation to 0 where ATen propagates it.
 
 Every comparison records its worst err / bound in ``PARITY`` (group, dtype); profiles/elem_fp64_parity.txt is that table.
@@ -896,6 +897,121 @@ def test_conv3x3_c1_wgrad_impulses(ops, dt):
         ops.conv3x3_c1_wgrad(x.to(DEV), to_act(ops, dY.view(B, H, W, Cout), dt), dW, ws)
         torch.cuda.synchronize()
         assert torch.equal(dW.view(Cout, 9).cpu().double(), taps[p].expand(Cout, 9)), p
+
+
+# ---- the first layer over its 16 x 16 tile list (SparK's sparse encoder) ---------------------------------------------------------------
+def c1_tile_list(B, H, W, count, g):
+    """A hand-built list of ``count`` distinct tiles in a fixed permutation; the entries past the count hold valid, UNLISTED tile ids.
+    -> (list int32 (dense tile count,), sel (B, H, W) float64: 1 at the pixels of the listed tiles)."""
+    tY, tX = -(-H // 16), -(-W // 16)
+    nt = B * tY * tX
+    assert 0 < count < nt
+    perm = torch.randperm(nt, generator=g)
+    tl = torch.cat([perm[:count], perm[count:][torch.arange(nt - count) % (nt - count)]]).to(torch.int32)
+    on = torch.zeros(nt, dtype=torch.float64)
+    on[perm[:count]] = 1.0
+    sel = on.view(B, tY, 1, tX, 1).expand(B, tY, 16, tX, 16).reshape(B, tY * 16, tX * 16)[:, :H, :W].contiguous()
+    return tl, sel
+
+
+def c1_tiles_chain(count, max_tiles, nchunk, cap, cout_fwd=None):
+    """The tile walk: min(max_tiles, cap) workgroups, workgroup i takes the list entries i, i + grid, ...: ceil(count / grid) tiles x
+    the pixels per thread and tile of the dense kernels; the same folds (``c1_chain``)."""
+    grid = min(max(int(max_tiles), 1), cap)
+    ppi = 256 // nchunk
+    fold = fold_k(nchunk, ppi)
+    if cout_fwd is not None and not (nchunk & (nchunk - 1) == 0 and nchunk <= 32 and cout_fwd <= 64):
+        fold = ppi - 1
+    return -(-count // grid) * -(-256 // ppi), fold
+
+
+# (B, H, W, chunks, listed tiles, max_tiles): partial tiles in both directions; a count below the host's bound (surplus workgroups write
+# zero rows); a non-power-of-two chunk count; more listed tiles than C1W_BLOCKS = 512 workgroups (two tiles for some of them)
+C1_TILE_CASES = [(2, 40, 56, 4, 9, 9), (3, 20, 37, 6, 5, 12), (1, 16, 48, 16, 2, 3), (4, 192, 192, 2, 530, 576)]
+
+
+def namespace_tiles(tl, count):
+    import types
+    return types.SimpleNamespace(list=tl.to(DEV), count=torch.tensor([count], dtype=torch.int32, device=DEV), tile_h=16, tile_w=16)
+
+
+@pytest.mark.parametrize("dt", DTS)
+@pytest.mark.parametrize("masked", [0, 2])
+@pytest.mark.parametrize("case", C1_TILE_CASES)
+def test_conv3x3_c1_over_a_tile_list(ops, dt, masked, case):
+    """cmu_conv3x3_c1_fwd_tiles and cmu_conv3x3_c1_wgrad_bn_tiles (reading and recomputing form) against the float64 references of the
+    dense entries, restricted to the listed tiles.  y: k=9 at the listed pixels, the sentinel elsewhere.  Statistics slab (rows summed in
+    float64 here): k = chain + fold + 9 / + 19 as in test_conv3x3_c1_fwd, with the chain of the tile walk.  dW: k = chain + fold +
+    K_APPLY as in test_conv3x3_c1_wgrad, both forms against the reference on the BITS the forward stored (the recomputing form must
+    reproduce them).  dA is non-zero in the unlisted tiles, which must not count."""
+    B, H, W, nchunk, count, max_tiles = case
+    Cout = nchunk * EPC[dt]
+    g = gen(1300 + H + masked)
+    x, w = torch.randn(B, H, W, generator=g), torch.randn(Cout, 1, 3, 3, generator=g) / 3
+    mask = c1_mask(masked, B, H, W, g)
+    mask_d = None if mask is None else mask.to(DEV)
+    tl, sel = c1_tile_list(B, H, W, count, g)
+    tiles = namespace_tiles(tl, count)
+    ya = empty_act(ops, B, H, W, Cout, dt, EPC[dt])
+    slab = ops.conv3x3_c1_fwd_tiles(*cuda(x, w), ya, tiles, max_tiles, mask_d, masked == 2)
+    torch.cuda.synchronize()
+    assert slab.shape == (min(max_tiles, C1F_CAP), 2, Cout)
+    ref, mag = R.c1_fwd_ref(x, w, mask, masked == 2)
+    on = sel.bool()
+    got = read(ya)
+    within(got[on], ref[on], elem_bound(ref[on], mag[on], 9, dt), "conv3x3_c1_fwd_tiles: y", dt)          # k=9
+    assert bool((got[~on] == SENT).all()) and slice_untouched(ya), "a pixel outside the listed tiles was written"
+    chain, fold = c1_tiles_chain(count, max_tiles, nchunk, C1F_CAP, Cout)
+    s = slab.double().sum(0).cpu()
+    rs, ms = ref * sel.unsqueeze(-1), mag * sel.unsqueeze(-1)
+    within(s[0], rs.sum((0, 1, 2)), (chain + fold + 9) * U * ms.sum((0, 1, 2)), "conv3x3_c1_fwd_tiles: stats sum", dt)
+    within(s[1], (rs * rs).sum((0, 1, 2)), (chain + fold + 19) * U * (ms * ms).sum((0, 1, 2)), "conv3x3_c1_fwd_tiles: stats sum of squares", dt)
+    # the weight gradient, on the raw output as stored (unlisted pixels: the reference there is masked out by ``sel``)
+    yraw = torch.where(on.unsqueeze(-1), got, quant(ref.float(), dt))
+    dA = data((B, H, W, Cout), dt, g, 1.0, 0.0)
+    sc, sh, mean, invstd = bn_vectors(yraw, g)
+    assert R.gate_is_safe(yraw, sc, sh)
+    coef = torch.randn(2, Cout, generator=g) * 0.1
+    ws = ws_bytes(lib().cmu_conv3x3_c1_wgrad_ws_bytes(B, H, W, Cout))
+    da = to_act(ops, dA, dt, EPC[dt])
+    r, m = R.bn_bwd_apply_ref(dA, yraw, sc, sh, mean, invstd, coef, sel=sel)
+    dref, dmag = R.c1_wgrad_ref(x, r, mask, masked == 2, mdY=m)
+    chain, fold = c1_tiles_chain(count, max_tiles, nchunk, C1W_BLOCKS)
+    for form, wf in (("read", None), ("recomputed", w.to(DEV))):
+        dW = torch.full((Cout, 1, 3, 3), SENT, device=DEV)
+        ops.conv3x3_c1_wgrad_bn_tiles(x.to(DEV), da, ya, *cuda(sc, sh, mean, invstd, coef), dW, ws, tiles, max_tiles, mask_d, masked == 2, w=wf)
+        torch.cuda.synchronize()
+        within(dW.view(Cout, 9), dref, (chain + fold + K_APPLY) * U * dmag, f"conv3x3_c1_wgrad_bn_tiles ({form}): dW", dt)
+
+
+@pytest.mark.parametrize("dt", DTS)
+def test_conv3x3_c1_wgrad_bn_tiles_impulses(ops, dt):
+    """dA = 1 at the last pixel of the last listed tile (a partial tile at the image's corner) and 2 in an unlisted tile, coef = 0, scale
+    1 with an open gate: dW[c][t] is the image's neighbour of that pixel at tap t (k = K_APPLY: the apply expression on one term, zeros
+    added), and the 2.0 does not count."""
+    B, H, W, nchunk = 2, 20, 37, 4
+    Cout = nchunk * EPC[dt]
+    g = gen(1400)
+    x, w = torch.randn(B, H, W, generator=g), torch.randn(Cout, 1, 3, 3, generator=g) / 3
+    tY, tX = 2, 3
+    last, other = B * tY * tX - 1, 1
+    tl = torch.tensor([0, 4, last] + [other] * (B * tY * tX - 3), dtype=torch.int32)
+    tiles = namespace_tiles(tl, 3)
+    ya = empty_act(ops, B, H, W, Cout, dt)
+    ops.conv3x3_c1_fwd_tiles(*cuda(x, w), ya, tiles, 3, want_stats=False)
+    dA = torch.zeros(B, H, W, Cout)
+    dA[B - 1, H - 1, W - 1] = 1.0
+    dA[0, 3, 16 + 5] = 2.0                                   # tile 1 of image 0: named by the entries past the count only
+    one, zero, big = torch.ones(Cout), torch.zeros(Cout), torch.full((Cout,), 100.0)
+    coef = torch.zeros(2, Cout)
+    ws = ws_bytes(lib().cmu_conv3x3_c1_wgrad_ws_bytes(B, H, W, Cout))
+    taps = R.c1_taps(x.double())[B - 1, H - 1, W - 1]
+    for form, wf in (("read", None), ("recomputed", w.to(DEV))):
+        dW = torch.full((Cout, 1, 3, 3), SENT, device=DEV)
+        ops.conv3x3_c1_wgrad_bn_tiles(x.to(DEV), to_act(ops, dA, dt), ya, *cuda(one, big, zero, one, coef), dW, ws, tiles, 3, w=wf)
+        torch.cuda.synchronize()
+        ref = taps.expand(Cout, 9)
+        within(dW.view(Cout, 9), ref, K_APPLY * U * ref.abs(), f"conv3x3_c1_wgrad_bn_tiles ({form}): impulse", dt)
 
 
 # ------------------------------------------------------------------------------------------------
