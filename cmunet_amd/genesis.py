@@ -320,12 +320,7 @@ class GenesisPretrainer(ArenaTrainer):
         if dp_exchanges(self.group):
             self._exchange_whole_arena()
             scale = 1.0 / self.world()
-        if self.amp is not None:
-            self.amp.check(self.flat.grad)
-            self.opt.step(grad_scale=scale, amp=self.amp)
-            self.amp.update()
-        else:
-            self.opt.step(grad_scale=scale)
+        self._checked_step(self.amp, grad_scale=scale)
         return loss
 
     @torch.no_grad()

@@ -106,24 +106,7 @@ class FlatParams:
 
     def gather_autograd_grads(self):
         """Copy ``p.grad`` tensors produced by autograd into the gradient arena (drop-in path)."""
-        dst, src, zero = [], [], []
-        _SINKS_CLAIMED.difference_update(id(p) for p in self.params.values())
-        for n in self.names:
-            g = self.params[n].grad
-            gv = self.grad_views[n]
-            if g is None:
-                zero.append(gv)
-            elif g.data_ptr() != gv.data_ptr():
-                if g.dtype == gv.dtype and g.shape == gv.shape:
-                    dst.append(gv)
-                    src.append(g.detach())
-                else:
-                    gv.copy_(g)
-        # a few multi-tensor launches instead of one copy per parameter (the joint model has ~270 small ones: 1.8 ms of launches)
-        if zero:
-            torch._foreach_zero_(zero)
-        if dst:
-            torch._foreach_copy_(dst, src)
+        self.gather_names(self.names)
 
     def gather_names(self, names):
         """``gather_autograd_grads`` restricted to ``names`` (one bucket of an overlapped exchange): their ``p.grad`` tensors into the
@@ -141,6 +124,7 @@ class FlatParams:
                     src.append(g.detach())
                 else:
                     gv.copy_(g)
+        # a few multi-tensor launches instead of one copy per parameter (the joint model has ~270 small ones: 1.8 ms of launches)
         if zero:
             torch._foreach_zero_(zero)
         if dst:

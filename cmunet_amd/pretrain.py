@@ -15,8 +15,8 @@ AmpOptimWrapper.update_params -> AdamW.step, cmunet_config.py:76-91) is ONE kern
 exactly the "masked-recon only" configuration SURVEY 8(d)-(2) names; the joint step lives in cmunet.py.
 """
 import math
-import time
 import os
+from time import perf_counter as _host_clock
 
 import numpy as np
 import torch
@@ -67,38 +67,112 @@ def default_amp(model, amp):
     return amp
 
 
+# ---- one step's data-parallel gradient exchange over a ``FlatParams`` gradient arena ---------------------------------------------------
+# What DDP's bucketed all-reduce gives the reference (Spark/main.py:102, dist_train.sh:9-17 + cmunet_config.py:120, Lightning's DDP): a
+# bucket's SUM all-reduce starts while the backward pass is still running, all of them are waited for before the inf / nan check, and the
+# step reports what was hidden under the backward and what was not.  The trainers below (and genesis.py) decide WHEN a range of the arena
+# is final; everything about the collectives themselves -- work handles, the late-write snapshots, the timed wait, the report -- lives in
+# ``GradExchange`` and nowhere else.
 _TEST_AFTER_LAUNCH = None      # test hook: callable(flat, lo, hi) run right after a bucket's exchange was started (tests/dp_child.py)
 
-
-def _start_bucket_exchange(flat, lo, hi, group, snapshots):
-    """Start the SUM all-reduce of arena gradient elements [lo, hi).  ``snapshots`` is None in normal operation.  In the debug mode
-    CMU_DP_CHECK_LATE_WRITES=1 (one-rank groups: the SUM is an identity) it is a list: the collective then runs on a COPY of the range
-    taken now, the arena keeps the producer's values, and ``_check_bucket_snapshots`` compares the two after the waits -- any write
-    into the range behind the launch shows, whichever side of the collective's own read / write-back it would have landed on."""
-    if snapshots is not None and dp_exchanges(group) and hi > lo:
-        snap = flat.grad[lo:hi].clone()
-        snapshots.append((lo, hi, snap))
-        w = dist.all_reduce(snap, op=dist.ReduceOp.SUM, group=group, async_op=True)
-    else:
-        w = flat.all_reduce_range_async(lo, hi, group)
-    if _TEST_AFTER_LAUNCH is not None and w is not None:
-        _TEST_AFTER_LAUNCH(flat, lo, hi)
-    return w
+# how a bucket was started -> the report's byte counter: from inside a fused node ("early"), from autograd's hooks ("in_backward") or only
+# after the backward pass ("flushed": nothing left to hide it under, so its bytes are the exposed ones)
+_BYTES = {"early": "bytes_early", "in_backward": "bytes_in_backward", "flushed": "exposed_bytes"}
 
 
-def _check_bucket_snapshots(flat, snaps, group):
-    if not snaps:
-        return
-    if dp_world(group) != 1:
-        raise RuntimeError("CMU_DP_CHECK_LATE_WRITES=1 compares a bucket with a copy taken at the launch of an IDENTITY all-reduce: use it on a one-rank group")
-    for lo, hi, snap in snaps:
-        now = flat.grad[lo:hi]
-        if not torch.equal(snap.view(torch.int32), now.view(torch.int32)):         # bit for bit (NaNs included)
-            bad = (snap.view(torch.int32) != now.view(torch.int32)).nonzero()
-            first = int(bad[0]) + int(lo)
-            owner = next((n for n, (off, cnt) in flat.offsets.items() if off <= first < off + cnt), "?")
-            raise RuntimeError(f"gradient exchange: {int(bad.numel())} element(s) of the bucket [{lo}, {hi}) were written after its all-reduce had "
-                               f"started (first: arena index {first}, parameter {owner})")
+class GradExchange:
+    """``begin(n)``, then ``start(lo, hi, how)`` per bucket as its gradients become final, then ``finish()`` -- or ``abort()`` when the
+    step raised in between.  ``starter(lo, hi) -> work or None`` replaces the plain all-reduce of a range (``flat.all_reduce_range_async``);
+    ``timed`` (the trainers' ``time_exchange``) brackets the waits of ``finish()`` with clocks; ``last`` is the step's report.
+
+    CMU_DDP_OVERLAP=0 (``overlap``): the owner exchanges the whole arena as one bucket behind the backward pass (A/B and fallback switch).
+
+    Debug mode CMU_DP_CHECK_LATE_WRITES=1 (``late_check``; meant for one-rank groups -- CMU_DP_REHEARSE=1 -- where the SUM all-reduce is an
+    identity): a bucket's collective runs on a COPY of its range taken when it STARTS, the arena keeps the producer's values, and the two
+    are compared after all exchanges were waited for -- a gradient written into a bucket after its all-reduce was launched (what the
+    in-forward announcements of SparK's fused node and the fused nodes' ``notify_ready`` must never allow) shows, whichever side of the
+    collective's own read / write-back it would have landed on, and raises instead of silently exchanging a stale value (advisor, round 4)."""
+
+    def __init__(self, flat, group=None, starter=None):
+        self.flat, self.group, self.starter = flat, group, starter
+        self.overlap = os.environ.get("CMU_DDP_OVERLAP", "1") != "0"
+        self.late_check = os.environ.get("CMU_DP_CHECK_LATE_WRITES", "0") == "1"
+        self.timed = False
+        self.active = False
+        self.works, self.snapshots, self.events, self.last = [], [], None, {}
+
+    def begin(self, n_buckets):
+        self.active = dp_exchanges(self.group)
+        self.works, self.snapshots, self.events = [], [], None
+        self.last = {"buckets": n_buckets, "early": 0, "in_backward": 0, "flushed": 0, "bytes_early": 0, "bytes_in_backward": 0,
+                     "exposed_bytes": 0}
+
+    def start(self, lo, hi, how):
+        """Start the SUM all-reduce of arena gradient elements [lo, hi) (async, on the group's stream) and count it under ``how``."""
+        if not self.active:
+            return
+        if self.late_check and hi > lo:
+            snap = self.flat.grad[lo:hi].clone()
+            self.snapshots.append((lo, hi, snap))
+            w = dist.all_reduce(snap, op=dist.ReduceOp.SUM, group=self.group, async_op=True)
+        elif self.starter is not None:
+            w = self.starter(lo, hi)
+        else:
+            w = self.flat.all_reduce_range_async(lo, hi, self.group)
+        if w is not None:
+            self.works.append(w)
+            if _TEST_AFTER_LAUNCH is not None:
+                _TEST_AFTER_LAUNCH(self.flat, lo, hi)
+        self.last[how] += 1
+        self.last[_BYTES[how]] += 4 * int(hi - lo)
+
+    def finish(self):
+        """Wait for every exchange in flight, then compare the late-write snapshots.  TIMED when ``timed`` is set (bench.py, tests):
+        ``wait_ms`` is the host clock around the waits (what a blocking backend -- gloo -- costs the step), ``exposed_ms`` the time the
+        COMPUTE stream stood still for them (events on the current stream around the waits: on RCCL ``work.wait()`` only makes the stream
+        wait, the host runs on) -- resolved lazily by ``report()``, never by a synchronisation inside the step."""
+        timed = self.timed and self.works and self.flat.grad.is_cuda
+        if timed:
+            e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+            e0.record()
+            t0 = _host_clock()
+        for w in self.works:
+            w.wait()
+        if timed:
+            self.last["wait_ms"] = (_host_clock() - t0) * 1e3
+            e1.record()
+            self.events = (e0, e1)
+        self.works = []
+        snaps, self.snapshots = self.snapshots, []
+        if not snaps:
+            return
+        if dp_world(self.group) != 1:
+            raise RuntimeError("CMU_DP_CHECK_LATE_WRITES=1 compares a bucket with a copy taken at the launch of an IDENTITY all-reduce: use it on a one-rank group")
+        for lo, hi, snap in snaps:
+            now = self.flat.grad[lo:hi]
+            if not torch.equal(snap.view(torch.int32), now.view(torch.int32)):         # bit for bit (NaNs included)
+                bad = (snap.view(torch.int32) != now.view(torch.int32)).nonzero()
+                first = int(bad[0]) + int(lo)
+                owner = next((n for n, (off, cnt) in self.flat.offsets.items() if off <= first < off + cnt), "?")
+                raise RuntimeError(f"gradient exchange: {int(bad.numel())} element(s) of the bucket [{lo}, {hi}) were written after its all-reduce had "
+                                   f"started (first: arena index {first}, parameter {owner})")
+
+    def abort(self):
+        """The step raised while exchanges were in flight: wait for them before the exception travels on (the next step's arena writes
+        would race the un-waited collectives), then forget them (advisor, round 4)."""
+        try:
+            for w in self.works:
+                w.wait()
+        finally:
+            self.works, self.snapshots = [], []
+
+    def report(self):
+        """``last`` with the timed fields resolved (synchronises: call it outside the timed region)."""
+        rep = dict(self.last)
+        if self.events is not None:
+            self.events[1].synchronize()
+            rep["exposed_ms"] = float(self.events[0].elapsed_time(self.events[1]))
+        return rep
 
 
 # ---- sharded exchange of one big parameter (round 6; the joint step's projector.fc0.weight: 262,144 x 1,536 fp32 = 1.61 GB at 512 x 512) --------
@@ -165,7 +239,37 @@ def all_gather_shares_async(t, group=None):
     return _Works(works)
 
 
-class MaskedReconPretrainer:
+class _ExchangingTrainer:
+    """What both trainer families share: the step's gradient exchange (``self.exchange``, a ``GradExchange``) as bench.py and the tests
+    see it, and the optimiser step behind it."""
+
+    last_exchange = property(lambda self: self.exchange.last)
+    time_exchange = property(lambda self: self.exchange.timed, lambda self, on: setattr(self.exchange, "timed", on))
+
+    def exchange_report(self):
+        return self.exchange.report()
+
+    def _checked_step(self, amp, **kw):
+        """The optimiser step behind the exchange.  ``amp``: an ``ops.AmpScaler`` or None -- the inf / nan check runs on the EXCHANGED
+        gradients (every rank sees the same ones and takes the same decision), the optimiser kernel unscales or skips from the same
+        device state, the scale is updated afterwards."""
+        if amp is not None:
+            amp.check(self.flat.grad)
+            self._amp_agree(amp)
+            kw["amp"] = amp
+        self._opt_step(**kw)
+        if amp is not None:
+            amp.update()
+
+    # (hooks of the sharded exchange, JointPretrainer)
+    def _amp_agree(self, amp):
+        pass
+
+    def _opt_step(self, **kw):
+        self.opt.step(**kw)
+
+
+class MaskedReconPretrainer(_ExchangingTrainer):
     """One object = model + flat arenas + fused AdamW + (optional) data-parallel group."""
 
     def __init__(self, model, lr=1.5e-4, betas=(0.9, 0.95), weight_decay=0.05, eps=1e-8, rc_weight=1.0,
@@ -197,12 +301,14 @@ class MaskedReconPretrainer:
         # as the encoder backward has passed it; the four down blocks (4.7 M) at the end -- only that last 19 MB all-reduce is
         # not hidden under kernels.  (CMU_DDP_OVERLAP=0: one all-reduce of the whole arena after the backward pass -- A/B and
         # fallback switch)
-        overlap = os.environ.get("CMU_DDP_OVERLAP", "1") != "0"
-        self._dec_off = self.flat.tail_offset(("up_conv", "conv_last")) if overlap else None
-        self._bott = self.flat.prefix_range("double_conv.") if (overlap and self._dec_off is not None) else None
-        if self._bott is not None and self._bott[1] != self._dec_off:
+        self.exchange = GradExchange(self.flat, self.group)
+        n = int(self.flat.grad.numel())
+        dec_off = self.flat.tail_offset(("up_conv", "conv_last")) if self.exchange.overlap else None
+        self._dec = (dec_off, n) if dec_off is not None else None
+        self._bott = self.flat.prefix_range("double_conv.") if self._dec is not None else None
+        if self._bott is not None and self._bott[1] != dec_off:
             self._bott = None                       # (the bottleneck is expected right in front of the decoder)
-        self._pending = []
+        self._rest = (0, (self._bott or self._dec or (n, n))[0])
 
     def broadcast_parameters(self, src=0):
         if dp_exchanges(self.group):
@@ -233,86 +339,41 @@ class MaskedReconPretrainer:
         ops.masked_mse_fwd_bwd(logits, self.pred_channel, img, mask, self.loss, self._dlogits,
                                self.rc_weight * self.loss_scale, self._ws, self.amp)
         eng.grad_target, eng.grad_prefix = self.flat.grad_views, ""
-        self._pending = []
-        self._snaps = []
-        late_check = os.environ.get("CMU_DP_CHECK_LATE_WRITES", "0") == "1"      # debug: see ArenaTrainer.__init__
-        exch = dp_exchanges(self.group)
-        # what the exchange of this step looked like (bench.py prints it next to the RCCL world size): buckets, how many of them
-        # were started from inside the backward pass, bytes left for after it
-        self.last_exchange = {"buckets": 1 + (self._dec_off is not None) + (self._bott is not None), "early": 0, "in_backward": 0,
-                              "flushed": 0, "exposed_bytes": 4 * int(self.flat.grad.numel())}
-
-        def decoder_done():
-            if self._dec_off is not None:
-                self._pending.append(_start_bucket_exchange(self.flat, self._dec_off, self.flat.grad.numel(), self.group, self._snaps if late_check else None))
-                if exch:
-                    self.last_exchange["early"] += 1
-                    self.last_exchange["exposed_bytes"] -= 4 * int(self.flat.grad.numel() - self._dec_off)
-
-        def bottleneck_done():
-            if self._bott is not None:
-                self._pending.append(_start_bucket_exchange(self.flat, self._bott[0], self._bott[1], self.group, self._snaps if late_check else None))
-                if exch:
-                    self.last_exchange["early"] += 1
-                    self.last_exchange["exposed_bytes"] -= 4 * int(self._bott[1] - self._bott[0])
-
+        # what the exchange of this step looks like (bench.py prints it next to the RCCL world size): the decoder and the bottleneck
+        # start from inside the backward pass ("early"), the down blocks behind it ("flushed": the bytes left for after it)
+        self.exchange.begin(1 + (self._dec is not None) + (self._bott is not None))
         try:
-            eng.unet_backward(self.sd, ctx, self._dlogits, after_decoder=decoder_done, after_bottleneck=bottleneck_done)
+            eng.unet_backward(self.sd, ctx, self._dlogits, after_decoder=self._decoder_done, after_bottleneck=self._bottleneck_done)
+        except BaseException:
+            self.exchange.abort()       # (in-flight all-reduces are waited for before the exception travels on, as in ArenaTrainer)
+            raise
         finally:
             eng.grad_target = None
         return self.loss
 
+    def _decoder_done(self):
+        if self._dec is not None:
+            self.exchange.start(*self._dec, "early")
+
+    def _bottleneck_done(self):
+        if self._bott is not None:
+            self.exchange.start(*self._bott, "early")
+
     def exchange_gradients(self):
-        """Finish the data-parallel gradient SUM (the decoder bucket may already be in flight) and return 1/world."""
-        world = dp_world(self.group)
+        """Finish the data-parallel gradient SUM (the decoder and bottleneck buckets may already be in flight) and return 1/world."""
         if not dp_exchanges(self.group):
             return 1.0
-        if self._dec_off is not None:
-            rest_hi = self._bott[0] if self._bott is not None else self._dec_off
-            works = [w for w in self._pending if w is not None]
-            works.append(self.flat.all_reduce_range_async(0, rest_hi, self.group))
-            # timed like ArenaTrainer._wait_works when ``time_exchange`` is set: host clock around the waits + the compute stream's
-            # standstill (events), resolved by ``exchange_report()``
-            timed = getattr(self, "time_exchange", False) and self.device.type == "cuda"
-            if timed:
-                e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
-                e0.record()
-                t0 = time.perf_counter()
-            for w in works:
-                if w is not None:
-                    w.wait()
-            if timed:
-                self.last_exchange["wait_ms"] = (time.perf_counter() - t0) * 1e3
-                e1.record()
-                self._exposed_events = (e0, e1)
-            self._pending = []
-            snaps, self._snaps = getattr(self, "_snaps", []), []
-            _check_bucket_snapshots(self.flat, snaps, self.group)
-        else:
-            self.flat.all_reduce_mean(self.group)
-        return 1.0 / world
-
-    def exchange_report(self):
-        """``last_exchange`` with the timed fields resolved (synchronises: call it outside the timed region)."""
-        rep = dict(getattr(self, "last_exchange", {}) or {})
-        ev = getattr(self, "_exposed_events", None)
-        if ev is not None:
-            ev[1].synchronize()
-            rep["exposed_ms"] = float(ev[0].elapsed_time(ev[1]))
-        return rep
+        self.exchange.start(*self._rest, "flushed")
+        self.exchange.finish()
+        return 1.0 / dp_world(self.group)
 
     def step(self, img, mask):
         loss = self.forward_backward(img, mask)
-        scale = self.exchange_gradients() / self.loss_scale
-        if self.amp is not None:
-            self.amp.check(self.flat.grad)         # after the exchange: every rank sees the same inf / nan
-        self.opt.step(grad_scale=scale, amp=self.amp)
-        if self.amp is not None:
-            self.amp.update()
+        self._checked_step(self.amp, grad_scale=self.exchange_gradients() / self.loss_scale)
         return loss
 
 
-class ArenaTrainer:
+class ArenaTrainer(_ExchangingTrainer):
     """Data-parallel trainer for the autograd-wrapped pretraining models (``CM_UNet``, ``Moco_v2``, ``SparK``): what the
     reference gets from DistributedDataParallel + an optimiser object (Spark/main.py:102,130-140; dist_train.sh:9-17 with
     cmunet_config.py:76-91,120; Lightning's DDP for moco2_module.py:339-344) is here
@@ -327,7 +388,9 @@ class ArenaTrainer:
     Embedding all-gathers and SyncBN exchanges stay inside the models (cmunet.py, moco.py, spark.py); all of them use the
     default process group, as the reference's do."""
 
-    def __init__(self, model, optimizer, process_group=None):
+    _ov_active = False         # True from ``_begin_overlap`` to ``_end_overlap``: hooks and ``notify_ready`` start buckets only then
+
+    def __init__(self, model, optimizer, process_group=None, starter=None):
         self.model = model
         self.group = process_group
         self.flat = optimizer.flat
@@ -341,17 +404,9 @@ class ArenaTrainer:
         # the node returns) -- and runs under the rest of the backward pass; everything is waited for before the inf check.
         # For the joint model the 1.6 GB projector gradient, produced first, is exchanged under the whole conv backward.
         # CMU_DDP_OVERLAP=0: one all-reduce of the whole arena after loss.backward() (A/B and fallback switch).
-        self._overlap = os.environ.get("CMU_DDP_OVERLAP", "1") != "0"
+        self.exchange = GradExchange(self.flat, self.group, starter)
         self._buckets = [dict(lo=lo, hi=hi, names=names, pending=0, launched=False) for lo, hi, names in self.flat.buckets()]
         self._bucket_of = {n: b for b in self._buckets for n in b["names"]}
-        self._ov_active = False
-        self._works = []
-        # Debug mode (CMU_DP_CHECK_LATE_WRITES=1, meant for one-rank groups -- CMU_DP_REHEARSE=1 -- where the SUM all-reduce is an
-        # identity): every bucket's range is copied when its exchange STARTS and compared after all exchanges were waited for; a
-        # gradient written into a bucket after its all-reduce was launched (what the in-forward announcements of SparK's fused node
-        # and the fused nodes' ``notify_ready`` must never allow) raises instead of silently exchanging a stale value (advisor, round 4).
-        self._late_check = os.environ.get("CMU_DP_CHECK_LATE_WRITES", "0") == "1"
-        self._snapshots = []
         # (hooks hold the trainer weakly: a model that outlives its trainer keeps no arena alive, and a dead trainer's hooks are no-ops)
         import weakref
         me = weakref.ref(self)
@@ -376,21 +431,20 @@ class ArenaTrainer:
     def _begin_overlap(self):
         for b in self._buckets:
             b["pending"], b["launched"] = len(b["names"]), False
-        self._works = []
-        self._snapshots = []
+        self.exchange.begin(len(self._buckets))
         self._ov_active = True
-        # per step: how many buckets started from inside a fused node ("early"), from autograd's hooks ("in_backward") or only after
-        # the backward pass ("flushed"), with their bytes; "exposed_bytes" = the flushed ones (nothing left to hide them under)
-        self.last_exchange = {"buckets": len(self._buckets), "early": 0, "in_backward": 0, "flushed": 0, "bytes_early": 0,
-                              "bytes_in_backward": 0, "exposed_bytes": 0}
 
-    def _launch(self, b):
+    def _end_overlap(self):
+        """Forget this step's bucket state and give the claimed gradient sinks back."""
+        from .optim import _SINKS_CLAIMED
+        self._ov_active = False
+        _SINKS_CLAIMED.difference_update(id(p) for p in self.flat.params.values())
+
+    def _launch(self, b, how):
         """Gradients of bucket ``b`` are final: bring stragglers into the arena, start its all-reduce (async, on the group's stream)."""
         b["launched"] = True
         self.flat.gather_names(b["names"])
-        w = self._start_exchange(b["lo"], b["hi"])
-        if w is not None:
-            self._works.append(w)
+        self.exchange.start(b["lo"], b["hi"], how)
 
     def _on_grad(self, name):
         if not self._ov_active:
@@ -398,9 +452,7 @@ class ArenaTrainer:
         b = self._bucket_of[name]
         b["pending"] -= 1
         if b["pending"] == 0 and not b["launched"]:
-            self.last_exchange["in_backward"] += 1
-            self.last_exchange["bytes_in_backward"] += 4 * int(b["hi"] - b["lo"])
-            self._launch(b)
+            self._launch(b, "in_backward")
 
     def notify_ready(self, prefix, grads):
         """Called from inside a fused autograd node: every parameter gradient under ``prefix`` is final and sits in ``grads``.  Buckets
@@ -418,74 +470,30 @@ class ArenaTrainer:
                     break
             if ok:
                 b["launched"] = True          # (their hooks fire when the node returns: nothing left to do then)
-                self.last_exchange["early"] += 1
-                self.last_exchange["bytes_early"] += 4 * int(b["hi"] - b["lo"])
-                w = self._start_exchange(b["lo"], b["hi"])
-                if w is not None:
-                    self._works.append(w)
+                self.exchange.start(b["lo"], b["hi"], "early")
 
     def _finish_overlap(self):
         """After loss.backward(): buckets that never completed (parameters without a gradient: SparK's ``densify_projs``) in arena
         order -- the same order on every rank --, then wait for everything."""
-        self._ov_active = False
         for b in self._buckets:
             if not b["launched"]:
-                self.last_exchange["flushed"] += 1
-                self.last_exchange["exposed_bytes"] += 4 * int(b["hi"] - b["lo"])
-                self._launch(b)
-        from .optim import _SINKS_CLAIMED
-        _SINKS_CLAIMED.difference_update(id(p) for p in self.flat.params.values())
-        self._wait_works()
-        self._check_snapshots()
-
-    def _start_exchange(self, lo, hi):
-        return _start_bucket_exchange(self.flat, lo, hi, self.group, self._snapshots if self._late_check else None)
-
-    def _check_snapshots(self):
-        snaps, self._snapshots = self._snapshots, []
-        _check_bucket_snapshots(self.flat, snaps, self.group)
-
-    def _wait_works(self):
-        """Wait for every exchange in flight.  TIMED when ``self.time_exchange`` is set (bench.py, tests): ``wait_ms`` is the host clock
-        around the waits (what a blocking backend -- gloo -- costs the step), ``exposed_ms`` the time the COMPUTE stream stood still for
-        them (events on the current stream around the waits: on RCCL ``work.wait()`` only makes the stream wait, the host runs on) --
-        resolved lazily by ``exchange_report()``, never by a synchronisation inside the step."""
-        timed = getattr(self, "time_exchange", False) and self._works and torch.cuda.is_available() and self.device.type == "cuda"
-        if timed:
-            e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
-            e0.record()
-            t0 = time.perf_counter()
-        for w in self._works:
-            w.wait()
-        if timed:
-            self.last_exchange["wait_ms"] = (time.perf_counter() - t0) * 1e3
-            e1.record()
-            self._exposed_events = (e0, e1)
-        self._works = []
+                self._launch(b, "flushed")
+        self._end_overlap()
+        self.exchange.finish()
 
     def _abort_overlap(self):
         """A forward / backward raised while exchanges were in flight: wait for them (the next step's arena writes would race the
         un-waited collectives), give the claimed gradient sinks back, forget the bucket state (advisor, round 4)."""
-        from .optim import _SINKS_CLAIMED
-        self._ov_active = False
         try:
-            for w in self._works:
-                w.wait()
+            self.exchange.abort()
         finally:
-            self._works = []
-            self._snapshots = []
-            _SINKS_CLAIMED.difference_update(id(p) for p in self.flat.params.values())
-            for b in self._buckets:
-                b["pending"], b["launched"] = len(b["names"]), False
+            self._end_overlap()
 
-    def exchange_report(self):
-        """``last_exchange`` with the timed fields resolved (synchronises: call it outside the timed region)."""
-        rep = dict(getattr(self, "last_exchange", {}) or {})
-        ev = getattr(self, "_exposed_events", None)
-        if ev is not None:
-            ev[1].synchronize()
-            rep["exposed_ms"] = float(ev[0].elapsed_time(ev[1]))
-        return rep
+    def _exchange_whole_arena(self):
+        """One exchange behind the backward pass: the whole arena as a single flushed bucket."""
+        self.exchange.begin(1)
+        self.exchange.start(0, int(self.flat.grad.numel()), "flushed")
+        self.exchange.finish()
 
     @staticmethod
     def trainable(model):
@@ -521,49 +529,27 @@ class ArenaTrainer:
             p.grad = None
         if amp is not None:
             loss = loss * amp.state[:4].view(torch.float32)          # the current scale, a one-element device tensor
-        scale = 1.0
-        if self._overlap and dp_exchanges(self.group):
+        exch = dp_exchanges(self.group)
+        if exch and self.exchange.overlap:
             if not overlap_begun:
                 self._begin_overlap()
             # (a raise in the backward pass or in the waits: every arena trainer gets the cleanup SparKPretrainer.step has -- in-flight
             # all-reduces waited for, gradient sinks released, buckets reset -- before the exception travels on)
             try:
                 loss.backward()
-                self._ov_active = False
                 self._finish_overlap()
             except BaseException:
                 self._abort_overlap()
                 raise
-            scale = 1.0 / self.world()
         else:
             loss.backward()
             self.flat.gather_autograd_grads()
-            if dp_exchanges(self.group):
+            if exch:
                 self._exchange_whole_arena()
-                scale = 1.0 / self.world()
-        kw = {} if ema is None else {"ema": ema}
-        if amp is not None:
-            amp.check(self.flat.grad)                                # after the exchange: every rank takes the same decision
-            self._amp_agree(amp)
-            self._opt_step(grad_scale=scale / loss_scale, amp=amp, **kw)
-            amp.update()
-            for p in self.flat.params.values():
-                p.grad = None
-            return
-        self._opt_step(grad_scale=scale / loss_scale, **kw)
+        scale = 1.0 / self.world() if exch else 1.0
+        self._checked_step(amp, grad_scale=scale / loss_scale, **({} if ema is None else {"ema": ema}))
         for p in self.flat.params.values():       # the arena holds them; drop the per-tensor copies autograd made
             p.grad = None
-
-
-    # (hooks of the sharded exchange, JointPretrainer)
-    def _exchange_whole_arena(self):
-        dist.all_reduce(self.flat.grad, op=dist.ReduceOp.SUM, group=self.group)
-
-    def _amp_agree(self, amp):
-        pass
-
-    def _opt_step(self, **kw):
-        self.opt.step(**kw)
 
 
 class JointPretrainer(ArenaTrainer):
@@ -579,7 +565,7 @@ class JointPretrainer(ArenaTrainer):
         model.train()
         flat = self.trainable(model)
         opt = FusedAdam(flat, lr=lr, betas=betas, eps=eps, weight_decay=weight_decay, decoupled=True, decay_filter=cmunet_paramwise_decay)
-        super().__init__(model, opt, process_group)
+        super().__init__(model, opt, process_group, starter=self._start_sharded)
         amp = default_amp(model, amp)
         self.amp = ops.AmpScaler(self.device) if amp is True else (amp or None)
         self.opt.amp = self.amp
@@ -607,7 +593,7 @@ class JointPretrainer(ArenaTrainer):
         only valid on its own share: ``finish_pending()`` (called by a forward pre-hook of the two projectors, by ``state_dict`` and by
         ``close``) completes it."""
         name, tname = "projector.fc0.weight", "target_projector.fc0.weight"
-        if os.environ.get("CMU_DP_SHARD_PROJECTOR", "1") == "0" or not dp_exchanges(self.group) or self._late_check:
+        if os.environ.get("CMU_DP_SHARD_PROJECTOR", "1") == "0" or not dp_exchanges(self.group) or self.exchange.late_check:
             return
         if name not in self.flat.offsets or tname not in self.tflat.offsets:
             return
@@ -634,21 +620,16 @@ class JointPretrainer(ArenaTrainer):
         self._shard_hooks = []
         super().close()
 
-    def _start_exchange(self, lo, hi):
+    def _start_sharded(self, lo, hi):
+        """The exchange's starter: the bucket that holds the big parameter is all-reduced in front of and behind it, the parameter itself
+        reduce-scattered; every other range is all-reduced as usual."""
         sh = self._shard
         if sh is None or not (lo <= sh["lo"] and sh["hi"] <= hi):
-            return super()._start_exchange(lo, hi)
-        # the bucket that holds the big parameter: all-reduce in front of and behind it, reduce-scatter of the parameter itself
-        if getattr(self, "last_exchange", None) is not None:
-            self.last_exchange["reduce_scatter_bytes"] = 4 * int(sh["hi"] - sh["lo"])
+            return self.flat.all_reduce_range_async(lo, hi, self.group)
+        self.exchange.last["reduce_scatter_bytes"] = 4 * int(sh["hi"] - sh["lo"])
         return _Works([self.flat.all_reduce_range_async(lo, sh["lo"], self.group),
                        reduce_scatter_sum_async(self.flat.grad[sh["lo"]:sh["hi"]], self.group),
                        self.flat.all_reduce_range_async(sh["hi"], hi, self.group)])
-
-    def _exchange_whole_arena(self):
-        if self._shard is None:
-            return super()._exchange_whole_arena()
-        self._start_exchange(0, int(self.flat.grad.numel())).wait()
 
     def _amp_agree(self, amp):
         """With a sharded gradient a rank sees the SUMMED gradient only on its own share (elsewhere its local one): the inf / nan flags are
@@ -791,7 +772,7 @@ class SparKPretrainer(ArenaTrainer):
         """``loss_scale``: static scale applied to the loss gradient INSIDE the fused step (the activations' gradients are
         stored in the model's dtype) and divided out again by the optimiser kernel."""
         self.model.grad_scale = float(loss_scale)
-        begun = self._overlap and dp_exchanges(self.group)
+        begun = self.exchange.overlap and dp_exchanges(self.group)
         try:
             if begun:
                 for p in self.flat.params.values():
@@ -808,7 +789,6 @@ class SparKPretrainer(ArenaTrainer):
         finally:
             self.model.grad_scale = 1.0
             self.model._unit_backward = False
-            self._ov_active = False
         return loss.detach()
 
 

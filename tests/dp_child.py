@@ -79,7 +79,7 @@ def _run(mode, out, opts, world, rank, dev, P):
             mask = torch.from_numpy(P.create_random_patch_mask(2, 32, 16, 0.5, np.random.RandomState(dseed + it))).to(dev)
             mask = torch.cat([mask, mask], 2).contiguous()
             losses.append(float(tr.step(x, mask)))
-        res = {"losses": losses, "arena": tr.flat.arena.cpu(), "bufs": {n: b.cpu() for n, b in net.named_buffers()}}
+        res = {"losses": losses, "arena": tr.flat.arena.cpu(), "bufs": {n: b.cpu() for n, b in net.named_buffers()}, "exchange": tr.last_exchange}
     elif mode == "joint":
         from cmunet_amd import cmunet as C
         torch.manual_seed(0)

@@ -153,6 +153,193 @@ def test_one_rank_group_and_the_rehearsal_knob():
     assert res == "ok", res
 
 
+# ---- cmunet_amd.pretrain.GradExchange: one step's gradient exchange, driven without a model on the six-parameter stand-in arena ----------
+_STANDIN = (("down_conv1.w", 36), ("down_conv1.b", 8), ("double_conv.w", 24), ("up_conv1.w", 12), ("up_conv1.b", 4), ("conv_last.w", 8))
+
+
+def _standin_flat():
+    """A CPU stand-in for ``FlatParams`` (the arena itself is GPU-only): names, offsets and a gradient arena."""
+    from cmunet_amd.optim import FlatParams
+    flat = FlatParams.__new__(FlatParams)
+    flat.names, flat.offsets, o = [n for n, _ in _STANDIN], {}, 0
+    for n, sz in _STANDIN:
+        flat.offsets[n] = (o, sz)
+        o += sz
+    flat.grad = torch.zeros(o)
+    return flat
+
+
+def _fill(flat, rank, seed):
+    """This rank's own gradients into the arena; returns what ONE all-reduce of the whole arena makes of them."""
+    flat.grad.copy_(torch.randn(flat.grad.numel(), generator=torch.Generator().manual_seed(seed + 17 * rank)))
+    whole = flat.grad.clone()
+    dist.all_reduce(whole)
+    return whole
+
+
+def _three_buckets(ex, flat):
+    """The masked-reconstruction trainer's step: decoder tail and bottleneck early, the down blocks flushed."""
+    n, dec, bott = flat.grad.numel(), flat.tail_offset(("up_conv", "conv_last")), flat.prefix_range("double_conv.")
+    assert (dec, bott) == (68, (44, 68))
+    ex.begin(3)
+    ex.start(dec, n, "early")
+    ex.start(bott[0], bott[1], "early")
+    ex.start(0, bott[0], "flushed")
+    ex.finish()
+    return 4 * ((n - dec) + (bott[1] - bott[0])), 4 * bott[0]
+
+
+def _exchange_worker(rank, world, port, q):
+    os.environ["MASTER_ADDR"] = "127.0.0.1"
+    os.environ["MASTER_PORT"] = str(port)
+    for k in ("CMU_DP_REHEARSE", "CMU_DP_CHECK_LATE_WRITES", "CMU_DDP_OVERLAP"):
+        os.environ.pop(k, None)
+    dist.init_process_group("gloo", rank=rank, world_size=world)
+    try:
+        from cmunet_amd.pretrain import GradExchange, _Works, all_gather_shares_async, reduce_scatter_sum_async
+        flat = _standin_flat()
+        n = flat.grad.numel()
+        # three buckets == one all-reduce of the whole arena, bit for bit; the report counts every bucket once
+        ex = GradExchange(flat, None)
+        assert ex.overlap and not ex.late_check
+        whole = _fill(flat, rank, 1)
+        early_bytes, rest_bytes = _three_buckets(ex, flat)
+        assert torch.equal(flat.grad, whole)
+        rep = ex.report()
+        assert rep["early"] + rep["in_backward"] + rep["flushed"] == rep["buckets"] == 3, rep
+        assert (rep["early"], rep["flushed"], rep["bytes_early"], rep["exposed_bytes"]) == (2, 1, early_bytes, rest_bytes), rep
+        assert not ex.works and not ex.snapshots
+        # a custom starter (the joint trainer's path without a model): ONE bucket as all-reduce + reduce-scatter of the parameter in
+        # the middle + all-reduce, then the all-gather of the shares
+        lo, hi = flat.offsets["double_conv.w"][0], sum(flat.offsets["double_conv.w"])
+
+        def sharded(a, b):
+            assert a <= lo and hi <= b
+            return _Works([flat.all_reduce_range_async(a, lo), reduce_scatter_sum_async(flat.grad[lo:hi]), flat.all_reduce_range_async(hi, b)])
+        sx = GradExchange(flat, None, starter=sharded)
+        whole = _fill(flat, rank, 2)
+        sx.begin(1)
+        sx.start(0, n, "flushed")
+        sx.finish()
+        all_gather_shares_async(flat.grad[lo:hi]).wait()
+        assert torch.equal(flat.grad, whole)
+        assert sx.report()["flushed"] == sx.report()["buckets"] == 1 and sx.report()["exposed_bytes"] == 4 * n
+        # abort: what is in flight is waited for and forgotten; the next step on fresh gradients is an all-reduce again
+        _fill(flat, rank, 3)
+        ex.begin(3)
+        ex.start(68, n, "early")
+        ex.start(44, 68, "early")
+        assert len(ex.works) == 2
+        ex.abort()
+        assert ex.works == [] and ex.snapshots == []
+        whole = _fill(flat, rank, 4)
+        _three_buckets(ex, flat)
+        assert torch.equal(flat.grad, whole)
+        q.put((rank, "ok"))
+    except Exception as e:  # noqa: BLE001
+        q.put((rank, repr(e)))
+    finally:
+        dist.destroy_process_group()
+
+
+def test_grad_exchange_two_ranks_gloo():
+    """``GradExchange`` on two gloo ranks: the masked-reconstruction trainer's three buckets, a sharded custom starter and a step after an
+    ``abort()`` all leave the bits of one ``dist.all_reduce`` of the arena; the report follows the shared definition."""
+    ctx = mp.get_context("spawn")
+    q = ctx.Queue()
+    port = _free_port()
+    procs = [ctx.Process(target=_exchange_worker, args=(r, 2, port, q)) for r in range(2)]
+    for p in procs:
+        p.start()
+    res = [q.get(timeout=180) for _ in procs]
+    for p in procs:
+        p.join(timeout=60)
+    assert sorted(res) == [(0, "ok"), (1, "ok")], res
+
+
+def _late_write_worker(port, q):
+    os.environ.update(MASTER_ADDR="127.0.0.1", MASTER_PORT=str(port), CMU_DP_REHEARSE="1", CMU_DP_CHECK_LATE_WRITES="1")
+    dist.init_process_group("gloo", rank=0, world_size=1)
+    try:
+        from cmunet_amd import pretrain as exchange
+        flat = _standin_flat()
+        ex = exchange.GradExchange(flat, None)
+        assert ex.late_check
+        produced = _fill(flat, 0, 5)                    # (one rank: the SUM is an identity)
+        _three_buckets(ex, flat)                        # no late write: passes, and the arena is untouched
+        assert torch.equal(flat.grad, produced) and not ex.snapshots
+        fired = []
+
+        def late(fl, lo, hi):
+            if not fired:
+                fired.append((lo, hi))
+                fl.grad[lo:lo + 1] += 1.0
+        exchange._TEST_AFTER_LAUNCH = late
+        try:
+            _three_buckets(ex, flat)
+            raise AssertionError("the late write was not caught")
+        except RuntimeError as e:
+            assert fired == [(68, 92)] and "[68, 92)" in str(e) and "parameter up_conv1.w" in str(e) and "arena index 68" in str(e), str(e)
+        finally:
+            exchange._TEST_AFTER_LAUNCH = None
+        produced[68] += 1.0                             # the arena keeps the producer's values (the collectives ran on the copies)
+        assert torch.equal(flat.grad, produced) and not ex.works and not ex.snapshots
+        q.put("ok")
+    except BaseException as e:  # noqa: BLE001
+        q.put(repr(e))
+    finally:
+        dist.destroy_process_group()
+
+
+def test_grad_exchange_late_write_check_one_rank():
+    """CMU_DP_CHECK_LATE_WRITES=1 on a one-rank group (CMU_DP_REHEARSE=1): a clean step passes; a write into a range behind the start of
+    its exchange makes ``finish()`` raise, naming the range and the owning parameter."""
+    ctx = mp.get_context("spawn")
+    q = ctx.Queue()
+    p = ctx.Process(target=_late_write_worker, args=(_free_port(), q))
+    p.start()
+    res = q.get(timeout=180)
+    p.join(timeout=60)
+    assert res == "ok", res
+
+
+def test_gather_autograd_grads_is_gather_names_over_all_names():
+    """``FlatParams.gather_autograd_grads()`` against ``gather_names(names)`` on a stand-in with a missing gradient, one the producer wrote
+    in place (aliased), a foreign one and a foreign one of another dtype: identical arenas, claimed sinks given back."""
+    from cmunet_amd import optim
+
+    def standin():
+        flat = optim.FlatParams.__new__(optim.FlatParams)
+        shapes = {"none.w": (3, 4), "alias.w": (8,), "foreign.w": (2, 2, 3), "f64.w": (4,)}
+        flat.names, flat.params, flat.grad_views, o = list(shapes), {}, {}, 0
+        flat.grad = torch.full((sum(torch.Size(s).numel() for s in shapes.values()),), 7.0)       # stale values everywhere
+        g = torch.Generator().manual_seed(11)
+        for n, shp in shapes.items():
+            p = torch.nn.Parameter(torch.zeros(shp))
+            cnt = p.numel()
+            flat.params[n], flat.grad_views[n] = p, flat.grad[o:o + cnt].view(shp)
+            o += cnt
+            if n == "alias.w":
+                flat.grad_views[n].copy_(torch.randn(shp, generator=g))
+                p.grad = flat.grad_views[n].view_as(flat.grad_views[n])
+            elif n == "foreign.w":
+                p.grad = torch.randn(shp, generator=g)
+            elif n == "f64.w":
+                p.grad = torch.randn(shp, generator=g, dtype=torch.float64).to(torch.float32)
+                p.grad.data = p.grad.data.double()
+        return flat
+    a, b = standin(), standin()
+    for flat in (a, b):
+        optim._SINKS_CLAIMED.update(id(p) for p in flat.params.values())
+    a.gather_names(a.names)
+    b.gather_autograd_grads()
+    assert torch.equal(a.grad, b.grad)
+    assert not any(id(p) in optim._SINKS_CLAIMED for flat in (a, b) for p in flat.params.values())
+    want = torch.cat([torch.zeros(12), a.params["alias.w"].grad.reshape(-1), a.params["foreign.w"].grad.reshape(-1),
+                      a.params["f64.w"].grad.reshape(-1).float()])
+    assert torch.equal(a.grad, want) and a.params["f64.w"].grad.dtype == torch.float64
+
+
 @pytest.mark.parametrize("workload", ["recon", "moco", "joint", "spark"])
 def test_bench_self_launcher_eight_rank_environment(workload):
     """``python bench.py --gpus 8 --workload X`` up to the first GPU call (the driver's 8-GPU run is the first time RCCL

@@ -422,9 +422,10 @@ def test_no_gradient_is_written_behind_its_bucket_exchange(cuda, mode):
     assert "raised" not in ok
     for k in keys:
         assert np.all(np.isfinite(ok[k])) and ok[k] == plain[k], (k, ok[k], plain[k])
+    ex = ok["exchange"]
+    assert ex is not None and ex["early"] + ex["in_backward"] + ex["flushed"] == ex["buckets"], ex
     if mode != "recon":
-        ex = ok["exchange"]
-        assert ex is not None and ex["early"] + ex["in_backward"] >= 1, ex       # exchanges really started inside the step
+        assert ex["early"] + ex["in_backward"] >= 1, ex       # exchanges really started inside the step
     assert "raised" in bad and "after its all-reduce had started" in bad["raised"], bad
 
 
