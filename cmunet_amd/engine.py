@@ -551,30 +551,47 @@ class UNetEngine:
     # ------------------------------------------------------------------------------------------
     # full UNet (model.py:110-131): encoder writes its skips straight into the decoder's concat buffers
     # ------------------------------------------------------------------------------------------
-    def unet_forward(self, sd, x_bhw, training, mask=None, mask_per_sample=False):
-        B, H, W = x_bhw.shape
-        # concat buffers + affine arrays of the last shape are reused from step to step (no per-step fills) unless a
-        # training forward is still waiting for its backward: that one keeps them, this call gets fresh ones
+    def _claim_cats(self, sd, B, H, W, training):
+        """The decoder's concat buffers for one forward pass: (cats, owns).  The buffers + affine arrays of the last shape are reused
+        from step to step (no per-step fills) unless a training forward is still waiting for its backward: that one keeps them, this
+        call gets fresh ones."""
         key = (B, H, W, self.tdt)
         if self._cats_busy and (self._cats_owner is None or self._cats_owner() is None):
             self._cats_busy = False           # the forward that held them was dropped without a backward
-        owns = False
         if self._cats_busy:
-            cats = self.decoder_alloc(sd, B, H, W, "")
-        else:
-            if self._cats is None or self._cats[0] != key:
-                self._cats = (key, self.decoder_alloc(sd, B, H, W, ""))
-            cats = self._cats[1]
-            self._cats_busy = bool(training)
-            owns = True
+            return self.decoder_alloc(sd, B, H, W, ""), False
+        if self._cats is None or self._cats[0] != key:
+            self._cats = (key, self.decoder_alloc(sd, B, H, W, ""))
+        self._cats_busy = bool(training)
+        return self._cats[1], True
+
+    def unet_forward(self, sd, x_bhw, training, mask=None, mask_per_sample=False, head=True):
+        B, H, W = x_bhw.shape
+        cats, owns = self._claim_cats(sd, B, H, W, training)
         skip_out = [Act(c["buf"], c["Cup"], c["Cskip"]) for c in cats]
         skip_affine = [(c["scale"][c["Cup"]:], c["shift"][c["Cup"]:]) for c in cats]
         ectx = self.encoder_forward(sd, x_bhw, training, "", mask, mask_per_sample, skip_out, skip_affine)
-        dctx = self.decoder_forward(sd, ectx["latent"], ectx["skips"], training, "", cats, True)
+        dctx = self.decoder_forward(sd, ectx["latent"], ectx["skips"], training, "", cats, head)
         ctx = _Ctx(enc=ectx, dec=dctx)
         if owns and training:
             self._cats_owner = weakref.ref(ctx)
-        return dctx["logits"], ctx
+        return dctx.get("logits"), ctx
+
+    def unet_predict(self, sd, x_bhw, logit_threshold=0.0, lut=None, prob_class=None):
+        """Evaluation forward (running statistics; no counter or running buffer is written) ending in the fused prediction head
+        instead of the logits: returns (labels (B,H,W) uint8, prob (B,H,W) f32 or None).  ``lut``: max(K,2) uint8 output values on
+        the device; ``prob_class``: also return that class's softmax probability (the sigmoid for a one-channel head).  A training
+        forward that still waits for its backward keeps its concat buffers (``_claim_cats``): this call does not disturb it."""
+        B, H, W = x_bhw.shape
+        _, ctx = self.unet_forward(sd, x_bhw, False, head=False)
+        x = ctx["dec"]["out"]
+        wl = sd["conv_last.weight"]
+        K = wl.shape[0]
+        labels = torch.empty((B, H, W), dtype=torch.uint8, device=self.device)
+        prob = self._f32(B, H, W) if prob_class is not None else None
+        ops.head_predict(x, wl.detach().reshape(K, -1), sd["conv_last.bias"].detach(), labels, prob,
+                         0 if prob_class is None else prob_class, logit_threshold, lut)
+        return labels, prob
 
     def unet_backward(self, sd, ctx, dlogits, after_decoder=None, after_bottleneck=None):
         """``after_decoder`` / ``after_bottleneck``: called when every decoder / bottleneck parameter gradient has been queued

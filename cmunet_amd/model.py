@@ -17,6 +17,8 @@ initialisation, ``state_dict``, ``torch.save`` and the reference's checkpoint ke
 their ``forward`` is never called: the module's forward runs the fused kernel schedule of ``engine.py``
 inside one ``torch.autograd.Function``.  Inputs must be CUDA (ROCm) tensors -- there is no CPU fallback.
 """
+import math
+
 import torch
 import torch.nn as nn
 
@@ -232,6 +234,15 @@ class _BlockFn(torch.autograd.Function):
         return (None, None, None, gx, gskip, *out)
 
 
+def class_value_table(class_values, out_classes, device):
+    """``class_values`` of ``UNet.predict`` as the uint8 device table the prediction head reads: max(out_classes, 2) integers in 0..255."""
+    vals = [int(v) for v in class_values]
+    n = max(int(out_classes), 2)
+    if len(vals) != n or any(not 0 <= v <= 255 for v in vals):
+        raise ValueError(f"class_values must be {n} integers in 0..255, got {vals}")
+    return torch.tensor(vals, dtype=torch.uint8).to(device)
+
+
 class UNet(_EngineOwner, nn.Module):
     """U-Net: 4 down blocks, 1024-channel bottleneck, 4 up blocks, 1x1 head (model.py:84-131).
 
@@ -259,3 +270,35 @@ class UNet(_EngineOwner, nn.Module):
             raise ValueError(f"UNet expects (B,H,W) input like the reference (model.py:120), got {tuple(x.shape)}")
         names, params = _param_args(self)
         return _UNetFn.apply(self, x, mask, mask_per_sample, names, *params)
+
+    def predict(self, x, threshold=0.5, prob_class=None, class_values=None):
+        """Segment ``x`` (B,H,W) float32 cuda: uint8 labels (B,H,W) -- argmax of the logits (ties to the smaller index, like
+        ``torch.argmax``); for a one-channel head ``sigmoid(logit) > threshold``, compared as ``logit > log(t / (1 - t))`` in fp32 --
+        or ``(labels, prob)`` with ``prob_class``: the fp32 softmax probability of that class (the sigmoid for one channel, class 0).
+        ``class_values``: max(out_classes, 2) integers in 0..255 (or such a uint8 table on the device) written instead of the
+        indices.  Always evaluation semantics (running statistics, nothing tracked, no autograd) whatever ``self.training`` is; the
+        mode is not changed.  The head, the argmax and the probability are one kernel: no logits are written (``ops.head_predict``)."""
+        if x.dim() != 3:
+            raise ValueError(f"UNet.predict expects (B,H,W) input, got {tuple(x.shape)}")
+        K = self.conv_last.weight.shape[0]
+        if not 0.0 < float(threshold) < 1.0:
+            raise ValueError(f"UNet.predict: threshold must lie inside (0, 1), got {threshold}")
+        if prob_class is not None and not 0 <= int(prob_class) < max(K, 1):
+            raise ValueError(f"UNet.predict: prob_class {prob_class} outside 0..{max(K, 1) - 1}")
+        _require_cuda(x, "UNet.predict")
+        lut = None
+        if torch.is_tensor(class_values) and class_values.is_cuda:      # a table already on the device (Segmenter: no copy per call)
+            if class_values.dtype != torch.uint8 or class_values.numel() != max(K, 2):
+                raise ValueError(f"UNet.predict: a device class_values table must hold {max(K, 2)} uint8 values")
+            lut = class_values.contiguous()
+        elif class_values is not None:
+            lut = class_value_table(class_values, K, x.device)
+        t = float(threshold)
+        logit_thr = float(torch.tensor(math.log(t / (1.0 - t)), dtype=torch.float32))
+        with torch.no_grad():
+            eng = self._engine(x.device)
+            sd = _named_state(self)
+            eng.prepack(sd)
+            labels, prob = eng.unet_predict(sd, x.detach().float().contiguous(), logit_thr, lut,
+                                            None if prob_class is None else int(prob_class))
+        return labels if prob_class is None else (labels, prob)

@@ -259,6 +259,19 @@ def conv1x1_head_fwd(x, w, bias, logits):
          _p(_f32c(logits)), x.B, x.H, x.W, x.C, K, x.dt, _stream())
 
 
+def head_predict(x_act, w, bias, labels, prob=None, prob_class=0, logit_threshold=0.0, lut=None):
+    """The 1x1 head fused with its argmax (K >= 2) or ``logit > logit_threshold`` (K == 1): ``labels`` (B,H,W) uint8 receives the
+    class index (``lut[index]`` with ``lut``: max(K,2) uint8 values on the device), ``prob`` (B,H,W) f32 or None the softmax
+    probability of ``prob_class`` (the sigmoid for K == 1).  The logits are the bits ``conv1x1_head_fwd`` writes, never stored."""
+    K = w.shape[0]
+    assert labels.dtype == torch.uint8 and labels.is_contiguous() and tuple(labels.shape) == (x_act.B, x_act.H, x_act.W)
+    assert prob is None or (tuple(prob.shape) == tuple(labels.shape) and _f32c(prob) is prob)
+    assert lut is None or (lut.dtype == torch.uint8 and lut.is_contiguous() and lut.numel() == max(K, 2))
+    call("cmu_head_predict", x_act.ptr(), x_act.ld, _p(x_act.scale), _p(x_act.shift), _p(_f32c(w)), _p(_f32c(bias)),
+         float(logit_threshold), _p(lut), _p(labels), _p(prob), int(prob_class), x_act.B, x_act.H, x_act.W, x_act.C, K, x_act.dt, _stream())
+    return labels
+
+
 def apply_to_nchw(y, out=None):
     if out is None:
         out = torch.empty((y.B, y.C, y.H, y.W), dtype=torch.float32, device=y.buf.device)

@@ -128,6 +128,21 @@ int cmu_conv1x1_head_fwd(const void* x, int64_t ldx, const float* in_scale, cons
                          const float* w /*(K,C)*/, const float* bias, float* logits,
                          int B, int H, int W, int C, int K, int dt, void* stream);
 
+/* Prediction head: the same Conv2d(C,K,1) + argmax / threshold (+ one class's probability) in one pass; no logits reach memory.
+ * Per pixel: logit_k = exactly the bits cmu_conv1x1_head_fwd writes for the same x / transform / w / bias (same chunking, fmaf
+ * order and lane butterfly).  K >= 2: label = the smallest k whose logit equals the maximum (torch.argmax on finite values);
+ * K == 1: label = logit_0 > logit_threshold (the host passes log(t / (1 - t)) for a probability threshold t).  labels (B,H,W)
+ * uint8 receives lut[label] (lut: max(K,2) device bytes), or the label itself when lut is NULL.  prob (B,H,W) f32 or NULL:
+ * K >= 2: softmax probability of class prob_class, exp(l_pc - m) / sum_j exp(l_j - m) with m = max_j l_j; K == 1: sigmoid(logit_0)
+ * (prob_class must be 0); fp32 with the accurate expf.  A NaN logit gives an unspecified label (one of the lut's values) and an
+ * unspecified probability; it never traps.
+ * Arguments as cmu_conv1x1_head_fwd: K in 1..8; C / (16 / sizeof(dt)) a power of two <= 64; x 16-byte aligned, ldx a multiple of
+ * 16 / sizeof(dt) and >= C; scale / shift both set or both NULL.  labels and prob must be 4-byte aligned (labels are stored four
+ * pixels per 32-bit word); 0 <= prob_class < max(K,1) when prob is given.  Every violation returns CMU_ERR_ARG, nothing is launched. */
+int cmu_head_predict(const void* x, int64_t ldx, const float* in_scale, const float* in_shift,
+                     const float* w /*(K,C)*/, const float* bias /*(K)*/, float logit_threshold, const uint8_t* lut,
+                     uint8_t* labels, float* prob, int prob_class, int B, int H, int W, int C, int K, int dt, void* stream);
+
 /* pending transform applied, NHWC dt -> NCHW fp32 (module boundary of DoubleConv/DownBlock/UpBlock). */
 int cmu_apply_to_nchw(const void* y, int64_t ldy, const float* scale, const float* shift, int relu_from,
                       float* out, int B, int H, int W, int C, int dt, void* stream);
