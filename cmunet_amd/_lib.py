@@ -88,6 +88,9 @@ _SIGS = {
     "cmu_convT2x2_fwd": (_I, [_P, _L, _P, _P, _I, _P, _P, _P, _L, _I, _I, _I, _I, _I, _I, _P]),
     "cmu_conv1x1_head_fwd": (_I, [_P, _L, _P, _P, _P, _P, _P, _I, _I, _I, _I, _I, _I, _P]),
     "cmu_head_predict": (_I, [_P, _L, _P, _P, _P, _P, _F, _P, _P, _P, _I, _I, _I, _I, _I, _I, _I, _P]),
+    "cmu_extract_tiles": (_I, [_P, _I, _I, _I, _I, _P, _I, _P, _I, _P, _I, _I, _I, _I, _P, _P]),
+    "cmu_head_probs": (_I, [_P, _L, _P, _P, _P, _P, _P, _I, _P, _I, _I, _I, _I, _I, _I, _P]),
+    "cmu_blend_tiles": (_I, [_P, _I, _I, _I, _P, _I, _P, _I, _I, _I, _I, _I, _P, _P, _F, _P, _P, _P, _I, _P]),
     "cmu_apply_to_nchw": (_I, [_P, _L, _P, _P, _I, _P, _I, _I, _I, _I, _I, _P]),
     "cmu_nchw_to_nhwc": (_I, [_P, _P, _L, _I, _I, _I, _I, _I, _P]),
     "cmu_nhwc_to_nchw": (_I, [_P, _L, _P, _I, _I, _I, _I, _I, _P]),

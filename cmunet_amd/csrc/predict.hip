@@ -12,30 +12,11 @@
 // The probability: after the butterfly every lane of the group holds the logits of all four pixels, so lane u (< 4) keeps pixel u's and
 // computes ONE softmax / sigmoid per trip -- the accurate expf and the division run once per lane, not four times in every lane -- and
 // the group's first four lanes store four consecutive floats.  (Groups of one or two lanes, C = epc or 2 epc, compute per pixel.)
-#include "common.h"
+#include "head_math.h"      // PRED_MAX_K and head_prob: shared with cmu_head_probs (tiled_predict.hip)
 
-constexpr int PRED_MAX_K = 8;
 #ifndef CMU_HEADP_CAP
 #define CMU_HEADP_CAP 8192
 #endif
-
-// softmax probability of class pc (K >= 2; m = the maximum logit) or the sigmoid (K == 1), fp32 with the accurate expf
-template <int KT>
-__device__ static inline float head_prob(const float* l, float m, int K, int pc) {
-    if (K == 1) {      // without overflow for either sign: the exponential's argument is never positive
-        const float e = expf(-fabsf(l[0]));
-        return (l[0] >= 0.f ? 1.f : e) / (1.f + e);
-    }
-    float s = 0.f, num = 0.f;
-#pragma unroll
-    for (int k = 0; k < KT; ++k)
-        if (k < K) {
-            const float e = expf(l[k] - m);
-            s += e;
-            num = (k == pc) ? e : num;
-        }
-    return num / s;
-}
 
 template <class TR, int KT, bool PROB>   // KT = compiled class count (2 for the reference's heads and one-channel heads, PRED_MAX_K otherwise)
 // (256 lanes; at least four waves per SIMD without the probability, three with it: the eight-class 16-bit form then takes 141 registers

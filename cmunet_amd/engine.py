@@ -593,6 +593,19 @@ class UNetEngine:
                          0 if prob_class is None else prob_class, logit_threshold, lut)
         return labels, prob
 
+    def unet_predict_probs(self, sd, x_bhw, codes=None, transposes=False, out=None):
+        """Evaluation forward as ``unet_predict``, ending in ``ops.head_probs``: every class's probability, (B, K', H, W) f32 with
+        K' = max(K, 1) (one sigmoid plane for a one-channel head).  ``codes``: B uint8 on the device, the dihedral code of the view
+        each image of ``x_bhw`` is in -- its planes come back in the un-augmented frame; ``out``: a (B, K', H, W) f32 buffer."""
+        B, H, W = x_bhw.shape
+        _, ctx = self.unet_forward(sd, x_bhw, False, head=False)
+        x = ctx["dec"]["out"]
+        wl = sd["conv_last.weight"]
+        K = wl.shape[0]
+        probs = self._f32(B, max(K, 1), H, W) if out is None else out
+        ops.head_probs(x, wl.detach().reshape(K, -1), sd["conv_last.bias"].detach(), probs, codes, transposes)
+        return probs
+
     def unet_backward(self, sd, ctx, dlogits, after_decoder=None, after_bottleneck=None):
         """``after_decoder`` / ``after_bottleneck``: called when every decoder / bottleneck parameter gradient has been queued
         (data-parallel trainers start those buckets' all-reduce there, under the rest of the backward pass)."""

@@ -4,11 +4,17 @@
   Segmenter(model, size=256, batch=32, ...).segment(images)   images of any size -> uint8 masks at the images' own sizes
   segment_files(model, paths, out_dir)                    ``.npy`` images -> ``<stem>_mask.npy``
   python -m cmunet_amd.infer --model M --images DIR --out DIR [--size 256] [--batch 32] [--dtype f16] [--threshold 0.5]
+                              [--tile 256 [--stride 128] [--window gaussian] [--pad reflect]] [--tta d4]
 
 Per chunk of same-sized images: the training pipeline's resize (``ops.resize_bicubic``: Pillow's bicubic in the image's own
 arithmetic, mode 'F' for float32 / mode 'L' for uint8, as ``dataset.DeviceSegmentationBatch`` feeds finetuning) -> ``UNet.predict``
 (the fused prediction head: no logits, no int64 argmax map) -> ``ops.resize_nearest`` back to the source size.  Everything runs on
 the HIP kernels; there is no CPU fallback.
+
+With ``tile`` and / or ``tta`` the chunk runs the tiled path instead (csrc/tiled_predict.hip): ``ops.extract_tiles`` cuts overlapping
+windows (in every flip / rotation asked for) out of the padded image, ``UNet.predict_probs`` writes every class's probability of each
+tile back in the image's frame, ``ops.blend_tiles`` sums them under a window in a fixed order and takes the argmax / threshold.
+``size=None`` then means the image's own resolution, whatever its size.
 """
 import argparse
 import os
@@ -64,15 +70,61 @@ def _depth(model):
     return n + 1
 
 
+def tile_starts(L, T, stride):
+    """Window starts along a side of length ``L`` for tiles of ``T``: ``[0]`` if the side fits in one tile (the tile is padded),
+    else every ``stride`` from 0 while the tile ends before the side does, plus the last tile clamped to the end:
+    tile_starts(475, 256, 128) == [0, 128, 219]."""
+    L, T, stride = int(L), int(T), int(stride)
+    if L < 1 or T < 1 or not 1 <= stride <= T:
+        raise ValueError(f"tile_starts: need L >= 1, T >= 1 and 1 <= stride <= T, got L={L}, T={T}, stride={stride}")
+    return [0] if L <= T else list(range(0, L - T, stride)) + [L - T]
+
+
+WINDOWS = ("uniform", "gaussian")
+
+
+def blend_window(T, kind="gaussian"):
+    """The blending window along one side of a tile, (T,) float32 on the host: ``'uniform'`` all ones; ``'gaussian'`` centred on
+    (T - 1) / 2 with sigma T / 8, normalised to maximum 1 (computed in float64, then cast)."""
+    T = int(T)
+    if T < 1:
+        raise ValueError(f"blend_window: T={T} must be at least 1")
+    if kind == "uniform":
+        return torch.ones(T, dtype=torch.float32)
+    if kind != "gaussian":
+        raise ValueError(f"blend_window: kind must be one of {WINDOWS}, got {kind!r}")
+    d = (np.arange(T, dtype=np.float64) - (T - 1) / 2.0) / (T / 8.0)
+    w = np.exp(-0.5 * d * d)
+    return torch.from_numpy((w / w.max()).astype(np.float32))
+
+
+TTA_CODES = {"flips": (0, 1, 2, 3), "d4": (0, 1, 2, 3, 4, 5, 6, 7)}
+# The probabilities of every (tile, copy) of the images blended together live in one float32 buffer (tiles x K' x T x T); images are
+# blended in groups whose buffer stays under this many bytes (a single image may exceed it: it is then a group of its own).
+PROB_BUDGET_BYTES = 1 << 30
+
+
 class Segmenter:
     """``segment(images)``: uint8 masks at each image's own size.
 
     ``size``: side the network runs at (the training pipeline's 256; None = each image's native size); ``batch``: images per
     network call; ``threshold``: probability threshold of a one-channel head; ``class_values``: max(out_classes, 2) integers in
-    0..255 written instead of the class indices.  ``size`` -- every image under ``size=None`` -- must be a multiple of
-    2**(depth-1)."""
+    0..255 written instead of the class indices.  ``size`` -- every image under ``size=None`` without ``tile`` -- must be a
+    multiple of 2**(depth-1).
 
-    def __init__(self, model, size=256, batch=32, threshold=0.5, class_values=None):
+    Tiled path (``tile`` or ``tta`` given; with both None the calls above run exactly as before):
+    ``tile``: side T of the square sliding window, a multiple of 2**(depth-1).  ``size``, when not None, is applied first (resize, then
+    tile); ``size=None`` runs at the image's own resolution, for ANY image size (a side shorter than T is padded: ``pad`` =
+    'reflect', without repeating the edge, or 'zero').  ``stride``: step of the window (default T // 2; 1 <= stride <= T); the last
+    window is clamped to the image's end.  ``window``: 'gaussian' (sigma T / 8) or 'uniform' weights of a tile's pixels in the blend.
+    ``tta``: None, 'flips' (the four flips), 'd4' (flips and 90-degree rotations: 8 copies) or a list of distinct dihedral codes (bit
+    0 flips W, bit 1 flips H, bit 2 transposes): the class probabilities are averaged over the copies.  With ``tile=None`` and
+    ``tta`` set every (resized) image is one tile of its own size (blended with uniform weights: one tile covers every pixel);
+    transposing codes then need square images (ValueError).  The network runs on at most ``batch`` tiles per call.  A one-channel
+    head thresholds the BLENDED probability."""
+
+    def __init__(self, model, size=256, batch=32, threshold=0.5, class_values=None, tile=None, stride=None, window="gaussian",
+                 pad="reflect", tta=None):
         self.model, self.size, self.batch, self.threshold = model, size, int(batch), threshold
         self.mult = 1 << (_depth(model) - 1)
         if size is not None and (int(size) <= 0 or int(size) % self.mult):
@@ -83,6 +135,31 @@ class Segmenter:
             raise ValueError(f"Segmenter: threshold must lie inside (0, 1), got {threshold}")
         self.class_values = None if class_values is None else [int(v) for v in class_values]
         self._lut = None
+        self.tile = None if tile is None else int(tile)
+        if self.tile is not None and (self.tile <= 0 or self.tile % self.mult):
+            raise ValueError(f"Segmenter: tile={tile} must be a positive multiple of {self.mult} (UNet depth {_depth(model)})")
+        if stride is not None and self.tile is None:
+            raise ValueError("Segmenter: stride needs tile")
+        self.stride = None if self.tile is None else (self.tile // 2 if stride is None else int(stride))
+        if self.stride is not None and not 1 <= self.stride <= self.tile:
+            raise ValueError(f"Segmenter: stride={stride} must lie in 1..tile={self.tile}")
+        if window not in WINDOWS:
+            raise ValueError(f"Segmenter: window must be one of {WINDOWS}, got {window!r}")
+        if pad not in ops.PAD_MODES:
+            raise ValueError(f"Segmenter: pad must be one of {sorted(ops.PAD_MODES)}, got {pad!r}")
+        self.window, self.pad = window, pad
+        if tta is None:
+            self.codes = None
+        elif isinstance(tta, str):
+            if tta not in TTA_CODES:
+                raise ValueError(f"Segmenter: tta must be None, one of {sorted(TTA_CODES)} or a list of codes, got {tta!r}")
+            self.codes = list(TTA_CODES[tta])
+        else:
+            self.codes = [int(c) for c in tta]
+            if not self.codes or len(set(self.codes)) != len(self.codes) or any(not 0 <= c <= 7 for c in self.codes):
+                raise ValueError(f"Segmenter: tta codes must be distinct integers in 0..7, got {list(tta)}")
+        self.tiled = self.tile is not None or self.codes is not None
+        self._grids = {}
 
     def _table(self, device):
         if self.class_values is None:
@@ -91,19 +168,67 @@ class Segmenter:
             self._lut = class_value_table(self.class_values, self.model.conv_last.weight.shape[0], device)
         return self._lut
 
-    def _chunk(self, src):
-        """src (n,H,W) float32 / uint8 on the device -> (n,H,W) uint8.  Launches only: no host synchronisation."""
+    def _grid(self, H, W, device):
+        """The tile grid + the two window vectors for (resized) images of H x W, built once per size (host checks, small uploads)."""
+        key = (H, W, device)
+        if key not in self._grids:
+            TH, TW = (self.tile, self.tile) if self.tile is not None else (H, W)
+            ys = tile_starts(H, TH, self.stride) if self.tile is not None else [0]
+            xs = tile_starts(W, TW, self.stride) if self.tile is not None else [0]
+            grid = ops.TileGrid(H, W, TH, TW, ys, xs, self.codes or (0,), device)
+            kind = self.window if self.tile is not None else "uniform"
+            self._grids[key] = (grid, blend_window(TH, kind).to(device), blend_window(TW, kind).to(device))
+        return self._grids[key]
+
+    def _chunk_tiled(self, x, prob_class):
+        """x (n,H,W) float32 / uint8 on the device, any H, W -> (labels (n,H,W) uint8, prob (n,H,W) f32 or None)."""
+        n, H, W = x.shape
+        grid, wy, wx = self._grid(H, W, x.device)
+        KP = max(int(self.model.conv_last.weight.shape[0]), 1)
+        labels = torch.empty((n, H, W), dtype=torch.uint8, device=x.device)
+        prob = torch.empty((n, H, W), dtype=torch.float32, device=x.device) if prob_class is not None else None
+        per_image = grid.per_image * KP * grid.TH * grid.TW * 4
+        group = max(1, min(n, PROB_BUDGET_BYTES // per_image))
+        probs = torch.empty((group * grid.per_image, KP, grid.TH, grid.TW), dtype=torch.float32, device=x.device)
+        tiles = torch.empty((group * grid.per_image, grid.TH, grid.TW), dtype=torch.float32, device=x.device)
+        for g0 in range(0, n, group):
+            g = min(group, n - g0)
+            nt = g * grid.per_image
+            ops.extract_tiles(x[g0:g0 + g], grid, self.pad, tiles[:nt])
+            codes = grid.tile_codes(g) if self.codes is not None else None
+            for c0 in range(0, nt, self.batch):
+                c1 = min(c0 + self.batch, nt)
+                self.model.predict_probs(tiles[c0:c1], None if codes is None else codes[c0:c1], probs[c0:c1])
+            ops.blend_tiles(probs[:nt], grid, wy, wx, labels[g0:g0 + g], None if prob is None else prob[g0:g0 + g],
+                            prob_class or 0, self.threshold, self._table(x.device))
+        return labels, prob
+
+    def _chunk(self, src, prob_class=None):
+        """src (n,H,W) float32 / uint8 on the device -> (n,H,W) uint8, or (labels, prob) with ``prob_class`` (prob at the size the
+        network ran at).  Launches only: no host synchronisation."""
         H, W = src.shape[1:]
         S = self.size
         x = src if S is None or (H, W) == (S, S) else ops.resize_bicubic(src, S, S)
-        if x.dtype == torch.uint8:      # 8-bit sources are resized in Pillow's mode-'L' arithmetic; the network reads float32
-            x = x.float()
-        lab = self.model.predict(x, threshold=self.threshold, class_values=self._table(src.device))
-        return lab if tuple(lab.shape[1:]) == (H, W) else ops.resize_nearest(lab, H, W)
+        if self.tiled:
+            lab, prob = self._chunk_tiled(x, prob_class)
+        else:
+            if x.dtype == torch.uint8:      # 8-bit sources are resized in Pillow's mode-'L' arithmetic; the network reads float32
+                x = x.float()
+            lab = self.model.predict(x, threshold=self.threshold, prob_class=prob_class, class_values=self._table(src.device))
+            lab, prob = lab if prob_class is not None else (lab, None)
+        lab = lab if tuple(lab.shape[1:]) == (H, W) else ops.resize_nearest(lab, H, W)
+        return lab if prob_class is None else (lab, prob)
 
-    def segment(self, images):
+    def segment(self, images, prob_class=None):
         """``images``: a list of 2-D arrays / tensors, or one (N,H,W) tensor; float32 or uint8, host or device, any sizes.  Returns
-        a list of (H,W) uint8 cuda tensors in input order.  Images are grouped by (shape, dtype) and run in chunks of ``batch``."""
+        a list of (H,W) uint8 cuda tensors in input order.  Images are grouped by (shape, dtype) and run in chunks of ``batch``.
+        With ``prob_class`` the list holds ``(mask, prob)`` pairs: ``prob`` is the float32 probability of that class (class 0 = the
+        sigmoid for a one-channel head; on the tiled path the blended one) AT THE SIZE THE NETWORK RAN AT: the image's own size
+        under ``size=None``, else ``size`` x ``size`` -- it is not resampled back."""
+        K1 = max(int(self.model.conv_last.weight.shape[0]), 1)
+        if prob_class is not None and not 0 <= int(prob_class) < K1:
+            raise ValueError(f"Segmenter.segment: prob_class {prob_class} outside 0..{K1 - 1}")
+        prob_class = None if prob_class is None else int(prob_class)
         dev = self.model.conv_last.weight.device
         if dev.type != "cuda":
             raise RuntimeError("Segmenter: the model must live on a CUDA/ROCm device; there is no CPU fallback in this package")
@@ -114,7 +239,7 @@ class Segmenter:
                 raise ValueError(f"Segmenter: every image must be 2-D, got {tuple(t.shape)}")
             if t.dtype != torch.uint8:
                 t = t.float()
-            if self.size is None and (t.shape[0] % self.mult or t.shape[1] % self.mult):
+            if self.size is None and self.tile is None and (t.shape[0] % self.mult or t.shape[1] % self.mult):
                 raise ValueError(f"Segmenter(size=None): image {tuple(t.shape)} is not a multiple of {self.mult}")
             items.append(t)
         groups = {}
@@ -125,8 +250,9 @@ class Segmenter:
             for c0 in range(0, len(idx), self.batch):
                 part = idx[c0:c0 + self.batch]
                 src = torch.stack([items[i].to(dev, non_blocking=True) for i in part]).contiguous()
-                for i, m in zip(part, self._chunk(src).unbind(0)):
-                    out[i] = m
+                res = self._chunk(src, prob_class)
+                for j, i in enumerate(part):
+                    out[i] = res[j] if prob_class is None else (res[0][j], res[1][j])
         return out
 
 
@@ -153,16 +279,25 @@ def main(argv=None):
     ap.add_argument("--model", required=True, help="best_model.pth of train() (a pickled module) or a state-dict file")
     ap.add_argument("--images", required=True, help="directory of 2-D .npy images (float32 or uint8)")
     ap.add_argument("--out", required=True, help="directory the <stem>_mask.npy files are written to")
-    ap.add_argument("--size", type=int, default=256, help="side the network runs at; 0 = each image's native size")
+    ap.add_argument("--size", type=int, default=None,
+                    help="side the network runs at (default 256; with --tile the default is the image's native size); 0 = native size")
     ap.add_argument("--batch", type=int, default=32)
     ap.add_argument("--dtype", default="f32", choices=["f32", "f16", "bf16"], help="storage type of the activations")
     ap.add_argument("--threshold", type=float, default=0.5, help="probability threshold of a one-channel head")
+    ap.add_argument("--tile", type=int, default=None, help="sliding-window inference with square tiles of this side (any image size)")
+    ap.add_argument("--stride", type=int, default=None, help="step of the sliding window (default tile // 2)")
+    ap.add_argument("--window", default="gaussian", choices=list(WINDOWS), help="weights of a tile's pixels where tiles overlap")
+    ap.add_argument("--pad", default="reflect", choices=sorted(ops.PAD_MODES), help="fill of a tile past an image smaller than it")
+    ap.add_argument("--tta", default="none", choices=["none"] + sorted(TTA_CODES),
+                    help="test-time augmentation: average the probabilities over the flips / over flips and 90-degree rotations")
     args = ap.parse_args(argv)
     if not torch.cuda.is_available():
         raise RuntimeError("cmunet_amd.infer needs a ROCm GPU; there is no CPU fallback in this package")
     model = load_segmentation_model(args.model, dtype=args.dtype)
     paths = sorted(os.path.join(args.images, f) for f in os.listdir(args.images) if f.endswith(".npy"))
-    written = segment_files(model, paths, args.out, size=args.size or None, batch=args.batch, threshold=args.threshold)
+    size = (None if args.tile else 256) if args.size is None else (args.size or None)
+    written = segment_files(model, paths, args.out, size=size, batch=args.batch, threshold=args.threshold, tile=args.tile,
+                            stride=args.stride, window=args.window, pad=args.pad, tta=None if args.tta == "none" else args.tta)
     print(f"{len(written)} masks written to {args.out}")
     return 0
 

@@ -302,3 +302,36 @@ class UNet(_EngineOwner, nn.Module):
             labels, prob = eng.unet_predict(sd, x.detach().float().contiguous(), logit_thr, lut,
                                             None if prob_class is None else int(prob_class))
         return labels if prob_class is None else (labels, prob)
+
+    def predict_probs(self, x, codes=None, out=None):
+        """Every class's probability of ``x`` (B,H,W) float32 cuda: (B, K', H, W) float32 -- the softmax of the logits for
+        out_classes >= 2 (K' = out_classes), the sigmoid for a one-channel head (K' = 1) -- computed by the head kernel itself; no
+        logits are written (``ops.head_probs``).  ``codes``: None, or B dihedral codes in 0..7 (a sequence, or a uint8 tensor on the
+        device), one per image: bit 0 = flipped along W, bit 1 = flipped along H, bit 2 = transposed (after the flips).  ``x`` is
+        ALREADY in that augmented view; the probabilities come back in the un-augmented frame.  A transposing code needs H == W.
+        ``out``: a (B, K', H, W) float32 cuda buffer to write into.  Evaluation semantics exactly as ``predict``."""
+        if x.dim() != 3:
+            raise ValueError(f"UNet.predict_probs expects (B,H,W) input, got {tuple(x.shape)}")
+        B, H, W = x.shape
+        transposes = H == W      # a device tensor of codes is not read back: on a square tile every code is valid
+        if codes is not None and not torch.is_tensor(codes):
+            vals = [int(c) for c in codes]
+            if len(vals) != B or any(not 0 <= c <= 7 for c in vals):
+                raise ValueError(f"UNet.predict_probs: codes must be {B} integers in 0..7, got {vals}")
+            transposes = any(c & 4 for c in vals)
+            if transposes and H != W:
+                raise ValueError(f"UNet.predict_probs: transposing codes need square images, got {H} x {W}")
+        elif codes is not None and (codes.dtype != torch.uint8 or codes.numel() != B):
+            raise ValueError(f"UNet.predict_probs: a codes tensor must hold {B} uint8 values")
+        _require_cuda(x, "UNet.predict_probs")
+        K = self.conv_last.weight.shape[0]
+        if out is not None and (tuple(out.shape) != (B, max(K, 1), H, W) or out.dtype != torch.float32 or not out.is_contiguous()
+                                or out.device != x.device):
+            raise ValueError(f"UNet.predict_probs: out must be a contiguous float32 ({B}, {max(K, 1)}, {H}, {W}) tensor on {x.device}")
+        if codes is not None:
+            codes = (codes if torch.is_tensor(codes) else torch.tensor(vals, dtype=torch.uint8)).to(x.device).contiguous()
+        with torch.no_grad():
+            eng = self._engine(x.device)
+            sd = _named_state(self)
+            eng.prepack(sd)
+            return eng.unet_predict_probs(sd, x.detach().float().contiguous(), codes, transposes and codes is not None, out)

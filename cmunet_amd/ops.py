@@ -272,6 +272,107 @@ def head_predict(x_act, w, bias, labels, prob=None, prob_class=0, logit_threshol
     return labels
 
 
+class TileGrid:
+    """The geometry the three tiled-prediction passes share, checked once on the host and kept on the device: images of size
+    (H, W), tiles (TH, TW) at ``ystarts`` x ``xstarts`` on the canvas max(H,TH) x max(W,TW), ``codes`` = the dihedral codes of the
+    copies made at every position (bit 0 flips W, bit 1 flips H, bit 2 transposes).  Raises ValueError for a start outside the
+    canvas, a pixel no tile covers, an invalid or repeated code, or a transposing code on a non-square tile."""
+
+    def __init__(self, H, W, TH, TW, ystarts, xstarts, codes=(0,), device="cuda"):
+        self.H, self.W, self.TH, self.TW = int(H), int(W), int(TH), int(TW)
+        self.ystarts, self.xstarts, self.codes = [int(v) for v in ystarts], [int(v) for v in xstarts], [int(c) for c in codes]
+        if min(self.H, self.W, self.TH, self.TW) < 1:
+            raise ValueError(f"TileGrid: sizes must be positive, got image {H} x {W}, tile {TH} x {TW}")
+        for name, starts, L, T in (("ystarts", self.ystarts, self.H, self.TH), ("xstarts", self.xstarts, self.W, self.TW)):
+            if not starts or sorted(set(starts)) != starts:
+                raise ValueError(f"TileGrid: {name} must be strictly increasing and not empty, got {starts}")
+            if starts[0] < 0 or starts[-1] + T > max(L, T):
+                raise ValueError(f"TileGrid: {name}={starts} leaves the canvas of {max(L, T)} for tiles of {T}")
+            gap = uncovered(starts, T, L)
+            if gap is not None:
+                raise ValueError(f"TileGrid: no tile covers index {gap} ({name}={starts}, tile {T}, length {L})")
+        if not self.codes or len(set(self.codes)) != len(self.codes) or any(not 0 <= c <= 7 for c in self.codes):
+            raise ValueError(f"TileGrid: codes must be distinct integers in 0..7, got {self.codes}")
+        self.transposes = any(c & 4 for c in self.codes)
+        if self.transposes and self.TH != self.TW:
+            raise ValueError(f"TileGrid: transposing codes {[c for c in self.codes if c & 4]} need a square tile, got {TH} x {TW}")
+        self.ny, self.nx, self.A = len(self.ystarts), len(self.xstarts), len(self.codes)
+        self.per_image = self.ny * self.nx * self.A
+        self.ys_dev = torch.tensor(self.ystarts, dtype=torch.int32).to(device)
+        self.xs_dev = torch.tensor(self.xstarts, dtype=torch.int32).to(device)
+        self.codes_dev = torch.tensor(self.codes, dtype=torch.uint8).to(device)
+        self._tile_codes = None
+
+    def tile_codes(self, n_images):
+        """The code of every tile of ``n_images`` images, in tile order (uint8 on the device; kept for the largest count asked)."""
+        n = n_images * self.per_image
+        if self._tile_codes is None or self._tile_codes.numel() < n:
+            self._tile_codes = self.codes_dev.repeat(n_images * self.ny * self.nx)
+        return self._tile_codes[:n]
+
+
+def uncovered(starts, T, L):
+    """The first index in [0, L) that none of the windows [s, s + T) covers, or None."""
+    end = 0
+    for s in sorted(starts):
+        if s > end:
+            break
+        end = max(end, s + T)
+    return None if end >= L else end
+
+
+PAD_MODES = {"zero": 0, "reflect": 1}
+
+
+def extract_tiles(src, grid, pad="reflect", out=None):
+    """``src`` (N,H,W) float32 / uint8 -> (N * ny * nx * A, TH, TW) float32: every window of ``grid`` in the forward view of each of
+    its codes; canvas pixels outside the image are zero (``pad='zero'``) or reflected without repeating the edge (``'reflect'``)."""
+    assert src.is_cuda and src.is_contiguous() and src.dim() == 3 and tuple(src.shape[1:]) == (grid.H, grid.W)
+    if src.dtype not in (torch.float32, torch.uint8):
+        raise ValueError(f"extract_tiles: the source must be float32 or uint8, got {src.dtype}")
+    if pad not in PAD_MODES:
+        raise ValueError(f"extract_tiles: pad must be one of {sorted(PAD_MODES)}, got {pad!r}")
+    N = src.shape[0]
+    if out is None:
+        out = torch.empty((N * grid.per_image, grid.TH, grid.TW), dtype=torch.float32, device=src.device)
+    assert tuple(out.shape) == (N * grid.per_image, grid.TH, grid.TW) and _f32c(out) is out
+    call("cmu_extract_tiles", _p(src), int(src.dtype == torch.uint8), N, grid.H, grid.W, _p(grid.ys_dev), grid.ny, _p(grid.xs_dev), grid.nx,
+         _p(grid.codes_dev), grid.A, grid.TH, grid.TW, PAD_MODES[pad], _p(out), _stream())
+    return out
+
+
+def head_probs(x_act, w, bias, probs, codes=None, transposes=False):
+    """The 1x1 head + softmax (K >= 2) / sigmoid (K == 1) storing every class: ``probs`` (n, K', H, W) f32, K' = max(K, 1) planes.
+    ``codes``: n uint8 on the device, the dihedral code of the view each image of ``x_act`` is in; its planes are stored in the
+    un-augmented frame.  ``transposes``: whether any code transposes (then H == W is required).  The logits are the bits
+    ``conv1x1_head_fwd`` writes, never stored."""
+    K = w.shape[0]
+    assert tuple(probs.shape) == (x_act.B, max(K, 1), x_act.H, x_act.W) and _f32c(probs) is probs
+    assert codes is None or (codes.dtype == torch.uint8 and codes.is_contiguous() and codes.numel() == x_act.B)
+    if transposes and x_act.H != x_act.W:
+        raise ValueError(f"head_probs: transposing codes need a square tile, got {x_act.H} x {x_act.W}")
+    call("cmu_head_probs", x_act.ptr(), x_act.ld, _p(x_act.scale), _p(x_act.shift), _p(_f32c(w)), _p(_f32c(bias)), _p(codes),
+         int(bool(transposes)), _p(probs), x_act.B, x_act.H, x_act.W, x_act.C, K, x_act.dt, _stream())
+    return probs
+
+
+def blend_tiles(probs, grid, wy, wx, labels, prob=None, prob_class=0, threshold=0.5, lut=None):
+    """``probs`` (N * ny * nx * A, K', TH, TW) f32 in the un-augmented frame -> ``labels`` (N,H,W) uint8: per pixel the covering tiles'
+    probabilities weighted by ``wy[y - y0] * wx[x - x0]`` and summed in the fixed order iy, ix, a; argmax (ties to the smaller
+    index) for K' >= 2, ``num / den > threshold`` for K' == 1; ``prob`` (N,H,W) f32 or None receives ``num[prob_class] / den``.
+    ``grid`` has checked that every pixel is covered."""
+    N = labels.shape[0]
+    KP = probs.shape[1]
+    assert labels.dtype == torch.uint8 and labels.is_contiguous() and tuple(labels.shape) == (N, grid.H, grid.W)
+    assert tuple(probs.shape) == (N * grid.per_image, KP, grid.TH, grid.TW) and _f32c(probs) is probs
+    assert _f32c(wy).numel() == grid.TH and _f32c(wx).numel() == grid.TW
+    assert prob is None or (tuple(prob.shape) == tuple(labels.shape) and _f32c(prob) is prob)
+    assert lut is None or (lut.dtype == torch.uint8 and lut.is_contiguous() and lut.numel() == max(KP, 2))
+    call("cmu_blend_tiles", _p(probs), N, grid.H, grid.W, _p(grid.ys_dev), grid.ny, _p(grid.xs_dev), grid.nx, grid.A, grid.TH, grid.TW, KP,
+         _p(wy), _p(wx), float(threshold), _p(lut), _p(labels), _p(prob), int(prob_class), _stream())
+    return labels
+
+
 def apply_to_nchw(y, out=None):
     if out is None:
         out = torch.empty((y.B, y.C, y.H, y.W), dtype=torch.float32, device=y.buf.device)

@@ -143,6 +143,37 @@ int cmu_head_predict(const void* x, int64_t ldx, const float* in_scale, const fl
                      const float* w /*(K,C)*/, const float* bias /*(K)*/, float logit_threshold, const uint8_t* lut,
                      uint8_t* labels, float* prob, int prob_class, int B, int H, int W, int C, int K, int dt, void* stream);
 
+/* Tiled (sliding-window) prediction with flip / rotation ensembling: three streaming passes (csrc/tiled_predict.hip).
+ * Geometry shared by the three: N images of one size (H,W); tiles TH x TW on the canvas max(H,TH) x max(W,TW), at the grid
+ * ystarts (ny) x xstarts (nx) (int32 device arrays); A augmented copies per position; tile index
+ * ((img * ny + iy) * nx + ix) * A + a.  Dihedral code of a copy: bit 0 flips W, bit 1 flips H, bit 2 transposes; the forward view
+ * applies flip W, flip H, transpose in that order, the inverse view undoes them.  Transposing codes need TH == TW.
+ *
+ * cmu_extract_tiles: src (N,H,W) float32 (src_u8 = 0) or uint8 (1) -> out (N*ny*nx*A, TH, TW) float32: the forward view, under
+ * codes[a] (A device bytes; NULL only with A == 1: code 0), of the window at (ystarts[iy], xstarts[ix]).  Window coordinates outside
+ * the image are filled by pad_mode: 0 = zero, 1 = reflection without repeating the edge (period 2 (L - 1); L == 1: that pixel).  A
+ * copy: exact.  The start arrays are read on the device: any value is safe (folded or zero-filled), a wrong one is a wrong tile.      */
+int cmu_extract_tiles(const void* src, int src_u8, int N, int H, int W, const int* ystarts, int ny, const int* xstarts, int nx,
+                      const uint8_t* codes, int A, int TH, int TW, int pad_mode, float* out, void* stream);
+/* cmu_head_probs: the head of cmu_head_predict (the same logits bit for bit, the same softmax / sigmoid arithmetic) storing every
+ * class's probability: probs (n, K', TH, TW) float32 with K' = K for K >= 2 and 1 (the sigmoid) for K == 1.  x holds n tiles of
+ * TH x TW pixels in their augmented view; codes (n device bytes, or NULL: all 0) gives each tile's dihedral code, and the tile's
+ * planes are stored in the un-augmented frame (the inverse view).  allow_transpose: 1 iff some code may have bit 2 set -- then
+ * TH == TW is required (a transposing code met on a non-square tile with allow_transpose = 0 is read without its bit 2).
+ * Other arguments and their rules as cmu_head_predict.  Every violation returns CMU_ERR_ARG, nothing is launched.                    */
+int cmu_head_probs(const void* x, int64_t ldx, const float* in_scale, const float* in_shift, const float* w /*(K,C)*/,
+                   const float* bias /*(K)*/, const uint8_t* codes, int allow_transpose, float* probs, int n, int TH, int TW, int C,
+                   int K, int dt, void* stream);
+/* cmu_blend_tiles: probs (N*ny*nx*A, K', TH, TW) -> labels (N,H,W) uint8 (+ prob (N,H,W) float32 or NULL).  Per pixel (y, x) the
+ * covering tiles are visited in the fixed order iy, ix, a ascending; weight = wy[y - y0] * wx[x - x0] (fp32 windows of TH and TW
+ * entries); num[k] = fmaf(weight, p[k], num[k]), den += weight.  K >= 2: label = the smallest k with the largest num[k]; K == 1:
+ * label = num[0] / den > threshold (a PROBABILITY threshold, fp32 division).  labels receives lut[label] (max(K,2) device bytes) or
+ * the label; prob receives num[prob_class] / den.  No atomics: the same bits on every call.  A pixel that no tile covers has
+ * den = 0 (label 0 / lut[0], probability NaN): the caller checks coverage from the start arrays on the host.                        */
+int cmu_blend_tiles(const float* probs, int N, int H, int W, const int* ystarts, int ny, const int* xstarts, int nx, int A, int TH,
+                    int TW, int K, const float* wy, const float* wx, float threshold, const uint8_t* lut, uint8_t* labels,
+                    float* prob, int prob_class, void* stream);
+
 /* pending transform applied, NHWC dt -> NCHW fp32 (module boundary of DoubleConv/DownBlock/UpBlock). */
 int cmu_apply_to_nchw(const void* y, int64_t ldy, const float* scale, const float* shift, int relu_from,
                       float* out, int B, int H, int W, int C, int dt, void* stream);
