@@ -210,6 +210,12 @@ _SIGS = {
     "cmu_mocoviews_noise": (_I, [_P, _I, _I, _P, _P, _P, _U64, _U64, _P]),
     "cmu_mse_ws_bytes": (_L, []),
     "cmu_mse_fwd_bwd": (_I, [_P, _I, _P, _P, _P, _F, _P, _I, _I, _I, _P, _P]),
+    "cmu_label_components_ws_bytes": (_L, [_I, _I, _I]),
+    "cmu_label_components": (_I, [_P, _I, _I, _P, _P, _I, _I, _I, _P, _P]),
+    "cmu_component_sizes": (_I, [_P, _P, _I, _I, _I, _P]),
+    "cmu_select_largest": (_I, [_P, _I, _P, _I, _I, _I, _P]),
+    "cmu_border_components": (_I, [_P, _P, _I, _I, _I, _P]),
+    "cmu_filter_components": (_I, [_P, _I, _P, _P, _I, _P, _I, _I, _P, _P, _P, _I, _P, _I, _I, _I, _P]),
     "cmu_amp_state_bytes": (_I, []),
     "cmu_amp_init": (_I, [_P, _F, _P]),
     "cmu_amp_check_finite": (_I, [_P, _L, _P, _P]),

@@ -5,6 +5,7 @@
   segment_files(model, paths, out_dir)                    ``.npy`` images -> ``<stem>_mask.npy``
   python -m cmunet_amd.infer --model M --images DIR --out DIR [--size 256] [--batch 32] [--dtype f16] [--threshold 0.5]
                               [--tile 256 [--stride 128] [--window gaussian] [--pad reflect]] [--tta d4]
+                              [--min-size 50] [--keep-largest 2] [--fill-holes] [--connectivity 8]
 
 Per chunk of same-sized images: the training pipeline's resize (``ops.resize_bicubic``: Pillow's bicubic in the image's own
 arithmetic, mode 'F' for float32 / mode 'L' for uint8, as ``dataset.DeviceSegmentationBatch`` feeds finetuning) -> ``UNet.predict``
@@ -22,7 +23,7 @@ import os
 import numpy as np
 import torch
 
-from . import ops
+from . import ops, postprocess
 from .model import UNet, _EngineOwner, class_value_table
 
 
@@ -121,10 +122,16 @@ class Segmenter:
     0 flips W, bit 1 flips H, bit 2 transposes): the class probabilities are averaged over the copies.  With ``tile=None`` and
     ``tta`` set every (resized) image is one tile of its own size (blended with uniform weights: one tile covers every pixel);
     transposing codes then need square images (ValueError).  The network runs on at most ``batch`` tiles per call.  A one-channel
-    head thresholds the BLENDED probability."""
+    head thresholds the BLENDED probability.
+
+    Clean-up (``min_size``, ``keep_largest`` or ``fill_holes`` given; with none of them the calls above run exactly as before):
+    ``postprocess.clean_mask`` runs on every mask AT THE IMAGE'S OWN SIZE (after the nearest-neighbour resize back, so ``min_size``
+    counts source pixels), on the plain and the tiled path, for every class but 0: components (``connectivity`` 4 or 8) of fewer
+    than ``min_size`` pixels are removed, then only the ``keep_largest`` (1..8) largest stay, then holes are filled.  The network and
+    blend passes then write class indices and the clean-up's last pass applies ``class_values``.  ``prob`` outputs are untouched."""
 
     def __init__(self, model, size=256, batch=32, threshold=0.5, class_values=None, tile=None, stride=None, window="gaussian",
-                 pad="reflect", tta=None):
+                 pad="reflect", tta=None, min_size=None, keep_largest=None, fill_holes=False, connectivity=8):
         self.model, self.size, self.batch, self.threshold = model, size, int(batch), threshold
         self.mult = 1 << (_depth(model) - 1)
         if size is not None and (int(size) <= 0 or int(size) % self.mult):
@@ -160,9 +167,24 @@ class Segmenter:
                 raise ValueError(f"Segmenter: tta codes must be distinct integers in 0..7, got {list(tta)}")
         self.tiled = self.tile is not None or self.codes is not None
         self._grids = {}
+        if min_size is not None and (isinstance(min_size, bool) or int(min_size) != min_size or int(min_size) < 0):
+            raise ValueError(f"Segmenter: min_size must be None or an integer >= 0, got {min_size!r}")
+        if keep_largest is not None and (isinstance(keep_largest, bool) or int(keep_largest) != keep_largest
+                                         or not 1 <= int(keep_largest) <= ops.CC_MAX_KEEP):
+            raise ValueError(f"Segmenter: keep_largest must be None or lie in 1..{ops.CC_MAX_KEEP}, got {keep_largest!r}")
+        if not isinstance(fill_holes, bool):
+            raise ValueError(f"Segmenter: fill_holes must be True or False, got {fill_holes!r}")
+        if connectivity not in (4, 8):
+            raise ValueError(f"Segmenter: connectivity must be 4 or 8, got {connectivity!r}")
+        self.min_size = None if min_size is None else int(min_size)
+        self.keep_largest = None if keep_largest is None else int(keep_largest)
+        self.fill_holes, self.connectivity = fill_holes, connectivity
+        self.post = self.min_size is not None or self.keep_largest is not None or self.fill_holes
 
-    def _table(self, device):
-        if self.class_values is None:
+    def _table(self, device, head=True):
+        """The class-value table; ``head``: for the prediction head / the blend, which write class indices when the mask is cleaned
+        afterwards (``cmu_filter_components`` applies the table instead: components are those of class indices)."""
+        if self.class_values is None or (head and self.post):
             return None
         if self._lut is None or self._lut.device != device:
             self._lut = class_value_table(self.class_values, self.model.conv_last.weight.shape[0], device)
@@ -217,6 +239,10 @@ class Segmenter:
             lab = self.model.predict(x, threshold=self.threshold, prob_class=prob_class, class_values=self._table(src.device))
             lab, prob = lab if prob_class is not None else (lab, None)
         lab = lab if tuple(lab.shape[1:]) == (H, W) else ops.resize_nearest(lab, H, W)
+        if self.post:      # on the mask at the image's own size: min_size counts source pixels
+            K = max(int(self.model.conv_last.weight.shape[0]), 2)
+            lab = postprocess.clean_mask(lab, range(1, K), self.min_size or 0, self.keep_largest, self.fill_holes, self.connectivity,
+                                         self._table(src.device, head=False))
         return lab if prob_class is None else (lab, prob)
 
     def segment(self, images, prob_class=None):
@@ -290,6 +316,10 @@ def main(argv=None):
     ap.add_argument("--pad", default="reflect", choices=sorted(ops.PAD_MODES), help="fill of a tile past an image smaller than it")
     ap.add_argument("--tta", default="none", choices=["none"] + sorted(TTA_CODES),
                     help="test-time augmentation: average the probabilities over the flips / over flips and 90-degree rotations")
+    ap.add_argument("--min-size", type=int, default=None, help="remove components of fewer than this many pixels of the source image")
+    ap.add_argument("--keep-largest", type=int, default=None, help="keep only this many (1..8) largest components of each class")
+    ap.add_argument("--fill-holes", action="store_true", help="fill the holes of each class")
+    ap.add_argument("--connectivity", type=int, default=8, choices=[4, 8], help="connectivity of the components")
     args = ap.parse_args(argv)
     if not torch.cuda.is_available():
         raise RuntimeError("cmunet_amd.infer needs a ROCm GPU; there is no CPU fallback in this package")
@@ -297,7 +327,8 @@ def main(argv=None):
     paths = sorted(os.path.join(args.images, f) for f in os.listdir(args.images) if f.endswith(".npy"))
     size = (None if args.tile else 256) if args.size is None else (args.size or None)
     written = segment_files(model, paths, args.out, size=size, batch=args.batch, threshold=args.threshold, tile=args.tile,
-                            stride=args.stride, window=args.window, pad=args.pad, tta=None if args.tta == "none" else args.tta)
+                            stride=args.stride, window=args.window, pad=args.pad, tta=None if args.tta == "none" else args.tta,
+                            min_size=args.min_size, keep_largest=args.keep_largest, fill_holes=args.fill_holes, connectivity=args.connectivity)
     print(f"{len(written)} masks written to {args.out}")
     return 0
 

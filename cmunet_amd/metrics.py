@@ -682,6 +682,36 @@ class radius_arteries(Metric):
         return (r[:, 0, 1] - r[:, 1, 1]).abs().mean()
 
 
+class components(Metric):
+    """The Betti-0 error (no reference counterpart): per image |components of argmax(prediction) - components of argmax(target)|,
+    batch value = fp64 mean over images.  Two-class (B,2,H,W) inputs, binarised by cmu_argmax2_mask as ``radius_arteries`` does (the
+    border is kept); labelled by cmu_label_components (csrc/components.hip) with ``connectivity`` 4 or 8.  No host sync."""
+    __name__ = "components"
+
+    def __init__(self, connectivity=8, **kwargs):
+        super().__init__(**kwargs)
+        if connectivity not in (4, 8):
+            raise ValueError(f"components: connectivity must be 4 or 8, got {connectivity!r}")
+        self.connectivity = connectivity
+
+    def per_image(self, y_pr, y_gt):
+        """(B, 2) int32: the component counts of prediction and target."""
+        _check_two_class(y_pr, y_gt, "components")
+        B, _, H, W = y_pr.shape
+        m = torch.empty(2 * B, H, W, dtype=torch.uint8, device=y_pr.device)
+        for k, x in enumerate((y_pr.detach(), y_gt.detach())):
+            if x.dtype not in (torch.float32, torch.float64):
+                x = x.float()
+            x = x.contiguous()
+            _lib.call("cmu_argmax2_mask", ops._p(x), int(x.dtype == torch.float64), ops._p(m[k * B:]), B, H, W, 0, ops._stream())
+        counts = ops.label_components(m, -1, self.connectivity)[1]
+        return torch.stack((counts[:B], counts[B:]), 1)
+
+    def forward(self, y_pr, y_gt):
+        c = self.per_image(y_pr, y_gt).double()
+        return (c[:, 0] - c[:, 1]).abs().mean()
+
+
 # ---------------------------------------------------------------------------------------------------
 # the rest of the reference's loss surface (metrics.py:495-551): L1Loss, MSELoss, BCELoss, BCEWithLogitsLoss (one-channel binary
 # heads) on cmu_pointwise_loss_fwd / _bwd; NLLLoss and RobustCrossEntropyLoss (class-index targets) on cmu_index_ce_fwd / _bwd

@@ -1278,3 +1278,75 @@ def random_patch_mask(B, H, W, patch_size=16, mask_ratio=0.65, seed=0, offset=0,
     m = torch.empty(B, H, W, dtype=torch.uint8, device=device)
     call("cmu_random_patch_mask", _p(m), B, H, W, patch_size, n_mask, int(seed) & (2 ** 64 - 1), int(offset), _stream())
     return m
+
+
+# ---- connected components of label maps (csrc/components.hip) ---------------------------------
+CC_MAX_KEEP = 8
+
+
+def _cc_check(what, t, dtype):
+    if not t.is_cuda:
+        raise RuntimeError(f"{what} runs on the GPU only; there is no CPU fallback in this package")
+    if t.dtype != dtype or t.dim() != 3 or not t.is_contiguous():
+        raise ValueError(f"{what}: a contiguous (B,H,W) {dtype} tensor, got {tuple(t.shape)} {t.dtype}")
+    B, H, W = t.shape
+    if B < 1 or H < 1 or W < 1 or H * W >= 2 ** 31 or B > 65535:
+        raise ValueError(f"{what}: 1 <= B <= 65535, 1 <= H, W and H * W < 2**31, got {tuple(t.shape)}")
+    return B, H, W
+
+
+def label_components(src, cls=-1, connectivity=8):
+    """src (B,H,W) uint8 -> (labels (B,H,W) int32, counts (B,) int32).  Foreground: ``src == cls`` (0..255), ``src != 0`` (-1) or
+    ``src != c`` (cls = -2 - c).  labels: 0 on background, else 1 + the smallest row-major index of the pixel's component."""
+    B, H, W = _cc_check("label_components", src, torch.uint8)
+    if connectivity not in (4, 8):
+        raise ValueError(f"label_components: connectivity must be 4 or 8, got {connectivity!r}")
+    if not -257 <= int(cls) <= 255:
+        raise ValueError(f"label_components: cls in 0..255, -1 or -2 - c, got {cls}")
+    labels = torch.empty(B, H, W, dtype=torch.int32, device=src.device)
+    counts = torch.empty(B, dtype=torch.int32, device=src.device)
+    ws = torch.empty(_lib.lib().cmu_label_components_ws_bytes(B, H, W), dtype=torch.uint8, device=src.device)
+    call("cmu_label_components", _p(src), int(cls), int(connectivity), _p(labels), _p(counts), B, H, W, _p(ws), _stream())
+    return labels, counts
+
+
+def component_sizes(labels):
+    """labels (B,H,W) int32 -> sizes (B,H,W) int32: flat entry r of an image holds the pixel count of label r + 1."""
+    B, H, W = _cc_check("component_sizes", labels, torch.int32)
+    sizes = torch.empty_like(labels)
+    call("cmu_component_sizes", _p(labels), _p(sizes), B, H, W, _stream())
+    return sizes
+
+
+def select_largest(sizes, n):
+    """sizes (B,H,W) int32 -> (B,n) int32: labels of the n largest components per image (ties: smaller label), -1 when unused."""
+    B, H, W = _cc_check("select_largest", sizes, torch.int32)
+    if not 1 <= int(n) <= CC_MAX_KEEP:
+        raise ValueError(f"select_largest: n must lie in 1..{CC_MAX_KEEP}, got {n}")
+    keep = torch.empty(B, int(n), dtype=torch.int32, device=sizes.device)
+    call("cmu_select_largest", _p(sizes), int(n), _p(keep), B, H, W, _stream())
+    return keep
+
+
+def border_components(labels):
+    """labels (B,H,W) int32 -> (B,H,W) uint8: flat entry r of an image is 1 iff label r + 1 has a pixel on the image's frame."""
+    B, H, W = _cc_check("border_components", labels, torch.int32)
+    touches = torch.empty(B, H, W, dtype=torch.uint8, device=labels.device)
+    call("cmu_border_components", _p(labels), _p(touches), B, H, W, _stream())
+    return touches
+
+
+def filter_components(src, cls, labels=None, sizes=None, min_size=0, keep_roots=None, removed_value=0, hole_labels=None,
+                      hole_touches=None, class_values=None):
+    """One pass over src (B,H,W) uint8 -> a new uint8 map: components of ``labels`` below ``min_size`` or missing from ``keep_roots``
+    receive ``removed_value``; pixels of ``hole_labels`` components that do not touch the frame receive ``cls``; ``class_values``
+    (uint8 device table) maps the result."""
+    B, H, W = _cc_check("filter_components", src, torch.uint8)
+    if int(min_size) < 0:
+        raise ValueError(f"filter_components: min_size must be >= 0, got {min_size}")
+    n_keep = 0 if keep_roots is None else int(keep_roots.shape[1])
+    out = torch.empty_like(src)
+    call("cmu_filter_components", _p(src), int(cls), _p(labels), _p(sizes), min(int(min_size), 2 ** 31 - 1), _p(keep_roots), n_keep,
+         int(removed_value), _p(hole_labels), _p(hole_touches), _p(class_values), 0 if class_values is None else class_values.numel(),
+         _p(out), B, H, W, _stream())
+    return out

@@ -905,6 +905,36 @@ int64_t cmu_mse_ws_bytes(void);
 int cmu_mse_fwd_bwd(const float* logits, int K, const float* y, float* loss, float* dlogits, float loss_scale, const void* amp_state,
                     int B, int H, int W, void* ws, void* stream);
 
+/* ---------------------------------------------------------------------------------------------
+ * Connected components of uint8 label maps and the clean-up of predicted masks (csrc/components.hip; no
+ * reference counterpart: users of the reference call scipy.ndimage on the host).  Shapes: 1 <= B <= 65535, 1 <= H, W,
+ * H * W < 2^31; B * H * W is indexed in 64 bits.  Every result is an integer: the same bits on every call.
+ *
+ * cmu_label_components: foreground = (src == cls) for cls in 0..255, (src != 0) for cls == -1, (src != c) for cls == -2 - c (the
+ * complement of class c, c in 0..255: what hole filling labels).  connectivity 4 or 8.  labels (B,H,W) int32: 0 on background,
+ * else 1 + the smallest row-major index y * W + x of the pixel's component within its image.  counts (B) int32: components per
+ * image, or -1 if a find / union walk of that image overran its trip bound of H * W (a defect, never expected).  Block-based
+ * union-find on 32 x 32 tiles; a fixed number of launches, no host synchronisation.  ws: cmu_label_components_ws_bytes.          */
+int64_t cmu_label_components_ws_bytes(int B, int H, int W);
+int cmu_label_components(const uint8_t* src, int cls, int connectivity, int32_t* labels, int32_t* counts, int B, int H, int W, void* ws,
+                         void* stream);
+/* sizes (B,H,W) int32: sizes[b, r] = pixels of the component labelled r + 1, 0 elsewhere (one atomic add per distinct label
+ * of a wave's 64 consecutive pixels; integer adds: exact in any order).                                                            */
+int cmu_component_sizes(const int32_t* labels, int32_t* sizes, int B, int H, int W, void* stream);
+/* keep_roots (B,n) int32, 1 <= n <= 8: the labels of the n largest components of each image, largest first, ties to the smaller
+ * label; unused slots -1.                                                                                                         */
+int cmu_select_largest(const int32_t* sizes, int n, int32_t* keep_roots, int B, int H, int W, void* stream);
+/* touches (B,H,W) uint8: touches[b, r] = 1 iff the component labelled r + 1 holds a pixel of the image's outer frame, else 0.   */
+int cmu_border_components(const int32_t* labels, uint8_t* touches, int B, int H, int W, void* stream);
+/* One streaming pass src (B,H,W) uint8 -> out (B,H,W) uint8 (another buffer).  With labels / sizes (both or neither; the labelling
+ * of class cls): a labelled pixel whose component has fewer than min_size pixels, or -- keep_roots (B,n_keep) given -- whose label
+ * is not listed for its image, receives removed_value.  With hole_labels / hole_touches (both or neither; the 4-connected labelling
+ * of cls = -2 - class and its cmu_border_components flags): a pixel of a component that does not touch the frame receives cls.
+ * class_values (n_values bytes, or NULL): out = class_values[v] for v < n_values.                                                  */
+int cmu_filter_components(const uint8_t* src, int cls, const int32_t* labels, const int32_t* sizes, int min_size, const int32_t* keep_roots,
+                          int n_keep, int removed_value, const int32_t* hole_labels, const uint8_t* hole_touches,
+                          const uint8_t* class_values, int n_values, uint8_t* out, int B, int H, int W, void* stream);
+
 /* Measurement support (bench.py's roofline block; no reference counterpart): the 16-bit MFMA rate this chip SUSTAINS.
  * Every wave of a one-workgroup-per-CU grid issues iters x 8 back-to-back 32x32x16 MFMAs from registers (no LDS, no
  * memory) or -- lds_fed = 1 -- the same MFMAs fed from LDS at the persistent conv kernel's ratio (6 fragment reads of 1 KB
