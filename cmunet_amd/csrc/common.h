@@ -238,6 +238,59 @@ __device__ static inline float wave_max(float v) {
     for (int o = 32; o > 0; o >>= 1) v = fmaxf(v, __shfl_xor(v, o, 64));
     return v;
 }
+// Block reductions over `red` (LDS, one word per wave), the result in every thread.  The order of the final sum decides the last bit:
+// the SEQUENTIAL family, for any wave count, adds the waves' sums in wave order from zero, ((0 + r0) + r1) + ...
+__device__ static inline float block_sum(float v, float* red /*[waves]*/) {
+    v = wave_sum(v);
+    __syncthreads();
+    if ((threadIdx.x & 63) == 0) red[threadIdx.x >> 6] = v;
+    __syncthreads();
+    float a = 0.f;
+    for (int i = 0; i < (int)(blockDim.x >> 6); ++i) a += red[i];
+    return a;
+}
+__device__ static inline double block_sum_d(double v, double* red /*[waves]*/) {
+    v = wave_sum_d(v);
+    __syncthreads();
+    if ((threadIdx.x & 63) == 0) red[threadIdx.x >> 6] = v;
+    __syncthreads();
+    double a = 0.0;
+    for (int i = 0; i < (int)(blockDim.x >> 6); ++i) a += red[i];
+    return a;
+}
+__device__ static inline float block_max(float v, float* red /*[waves]*/) {
+    v = wave_max(v);
+    __syncthreads();
+    if ((threadIdx.x & 63) == 0) red[threadIdx.x >> 6] = v;
+    __syncthreads();
+    float a = red[0];
+    for (int i = 1; i < (int)(blockDim.x >> 6); ++i) a = fmaxf(a, red[i]);
+    return a;
+}
+// ... and the PAIRWISE family, for blocks of exactly four waves (256 threads): (r0 + r1) + (r2 + r3)
+__device__ static inline float block_sum4(float v, float* red /*[4]*/) {
+    v = wave_sum(v);
+    __syncthreads();
+    if ((threadIdx.x & 63) == 0) red[threadIdx.x >> 6] = v;
+    __syncthreads();
+    return (red[0] + red[1]) + (red[2] + red[3]);
+}
+__device__ static inline float block_max4(float v, float* red /*[4]*/) {
+    v = wave_max(v);
+    __syncthreads();
+    if ((threadIdx.x & 63) == 0) red[threadIdx.x >> 6] = v;
+    __syncthreads();
+    return fmaxf(fmaxf(red[0], red[1]), fmaxf(red[2], red[3]));
+}
+// most blocks of a pass that leaves one partial per block in a workspace for a fixed-order finalisation (heads.hip, pointwise_loss.hip)
+constexpr int CE_MAX_BLOCKS = 1024;
+
+// index i of a border-reflected axis of n samples without edge repeat (OpenCV's BORDER_REFLECT_101, torch's "reflect" padding)
+__device__ static inline int reflect101(int i, int n) {
+    if (n == 1) return 0;
+    while (i < 0 || i >= n) i = i < 0 ? -i : 2 * n - 2 - i;
+    return i;
+}
 
 // SparK patch mask: pixel (y, x) of a level whose side is f << sbits looks up active[b][y >> sbits][x >> sbits]
 // (b, y, x) of pixel index p of a (B, H, W) grid.  ``small`` (uniform: the grid has fewer than 2^31 pixels -- every shape of the
@@ -278,6 +331,12 @@ __host__ __device__ static inline int cmu_div_up(int a, int b) { return (a + b -
 // rows per (slice, tap) of the packed 3x3 weights: [K/32B][9][npad][32 B]; 64 for narrow layers, else a multiple of 128
 __host__ __device__ static inline int cmu_conv3x3_npad(int N) { return N <= 64 ? 64 : ((N + 127) / 128) * 128; }
 static inline int64_t cmu_div_up64(int64_t a, int64_t b) { return (a + b - 1) / b; }
+// tail of the cmu_*_rec_layout exporters: the first n of a record's M layout words (size, then field offsets) go to out; returns M
+template <int M>
+static inline int cmu_export_layout(const int64_t (&v)[M], int64_t* out, int n) {
+    for (int i = 0; i < M && i < n; ++i) out[i] = v[i];
+    return M;
+}
 
 // counter-based Philox4x32-10 (Salmon et al., SC 2011): four 32-bit words of counter (c0..c3) under key (k0, k1)
 __device__ static inline void philox4x32_10(uint32_t c0, uint32_t c1, uint32_t c2, uint32_t c3, uint32_t k0, uint32_t k1, uint32_t* out) {

@@ -15,7 +15,7 @@
 // both, and the horizontal pass that reads an A pixel several times draws the same value each time.  An explicit float64 noise input
 // (2, B, S, S) -- plane 0 for GaussNoise, plane 1 for OneOf's GaussNoise -- replaces the generator for parity tests.
 // Built with -ffp-contract=off (Makefile): the restated double and float arithmetic rounds after every operation.
-#include "common.h"
+#include "philox_stream.h"
 #include "pillow_resample.h"
 #include <math.h>
 #include <stddef.h>
@@ -39,56 +39,17 @@ extern "C" int cmu_ftaug_rec_layout(int64_t* out, int n) {
                          (int64_t)offsetof(CmuFtAugRec, var_oneof), (int64_t)offsetof(CmuFtAugRec, sigma), (int64_t)offsetof(CmuFtAugRec, alpha),
                          (int64_t)offsetof(CmuFtAugRec, beta), (int64_t)offsetof(CmuFtAugRec, scale), (int64_t)offsetof(CmuFtAugRec, oneof),
                          (int64_t)offsetof(CmuFtAugRec, rot_k)};
-    const int m = (int)(sizeof(v) / sizeof(v[0]));
-    for (int i = 0; i < m && i < n; ++i) out[i] = v[i];
-    return m;
+    return cmu_export_layout(v, out, n);
 }
 
 // ---------------------------------------------------------------------------------------------
-// randomness.  Record stream: c0 counts the draws, c1 = purpose << 28 | image, (c2, c3) = offset, key = seed.  Pixel noise: c0 = pixel
-// of the crop (y * S + x), c1 = stage << 28 | image; Box-Muller on 53-bit uniforms in (0, 1).
+// randomness.  Record stream (PhiloxStream, philox_stream.h): c1 = purpose << 28 | image, (c2, c3) = offset, key = seed.  Pixel noise:
+// c0 = pixel of the crop (y * S + x), c1 = stage << 28 | image; Box-Muller on 53-bit uniforms in (0, 1).
 // ---------------------------------------------------------------------------------------------
-__device__ static inline uint32_t fta_id(int purpose, int img) { return ((uint32_t)purpose << 28) | (uint32_t)img; }
-struct FtaStream {
-    uint32_t k0, k1, id, o0, o1, c0;
-    uint32_t buf[4];
-    int pos;
-    __device__ FtaStream(uint64_t seed, uint64_t offset, uint32_t id_)
-        : k0((uint32_t)seed), k1((uint32_t)(seed >> 32)), id(id_), o0((uint32_t)offset), o1((uint32_t)(offset >> 32)), c0(0), pos(4) {}
-    __device__ uint32_t next() {
-        if (pos == 4) {
-            philox4x32_10(c0++, id, o0, o1, k0, k1, buf);
-            pos = 0;
-        }
-        return buf[pos++];
-    }
-    // random.random(): uniform on [0, 1), 53 bits
-    __device__ double uniform() {
-        const uint64_t hi = next(), lo = next();
-        return (double)(((hi << 32) | lo) >> 11) * (1.0 / 9007199254740992.0);
-    }
-    // random.uniform(a, b) = a + (b - a) * random()
-    __device__ double uniform(double a, double b) { return __dadd_rn(a, __dmul_rn(__dadd_rn(b, -a), uniform())); }
-    // uniform integer in [0, n): Lemire's multiply-shift with rejection
-    __device__ uint32_t below(uint32_t n) {
-        uint64_t m = (uint64_t)next() * n;
-        uint32_t l = (uint32_t)m;
-        if (l < n) {
-            const uint32_t t = (0u - n) % n;
-            while (l < t) {
-                m = (uint64_t)next() * n;
-                l = (uint32_t)m;
-            }
-        }
-        return (uint32_t)(m >> 32);
-    }
-};
 __device__ static inline double fta_normal(uint64_t seed, uint64_t offset, int stage, int b, int64_t pix) {
     uint32_t r[4];
-    philox4x32_10((uint32_t)pix, fta_id(stage, b), (uint32_t)offset, (uint32_t)(offset >> 32), (uint32_t)seed, (uint32_t)(seed >> 32), r);
-    const double u1 = ((double)((((uint64_t)r[0] << 32) | r[1]) >> 11) + 0.5) * (1.0 / 9007199254740992.0);
-    const double u2 = ((double)((((uint64_t)r[2] << 32) | r[3]) >> 11) + 0.5) * (1.0 / 9007199254740992.0);
-    return sqrt(-2.0 * log(u1)) * cos(6.283185307179586 * u2);
+    philox4x32_10((uint32_t)pix, philox_id(stage, b), (uint32_t)offset, (uint32_t)(offset >> 32), (uint32_t)seed, (uint32_t)(seed >> 32), r);
+    return sqrt(-2.0 * log(philox_u53_open(r[0], r[1]))) * cos(6.283185307179586 * philox_u53_open(r[2], r[3]));
 }
 // x + sigma * z in float64, optionally clipped to [0, 1] (albumentations' maximum for float32), stored as float32
 __device__ static inline float fta_add_noise(float x, double sigma, double z, int clip) {
@@ -108,7 +69,7 @@ __global__ __launch_bounds__(64) void ftaug_sample_kernel(CmuFtAugRec* __restric
     const int b = blockIdx.x * 64 + threadIdx.x;
     if (b >= B) return;
     const double* p = P.p;
-    FtaStream s(seed, offset, fta_id(FS_RECORD, b));
+    PhiloxStream s(seed, offset, philox_id(FS_RECORD, b));
     CmuFtAugRec r;
     r.ops = 0;
     r.y0 = min((int)((double)(H - crop + 1) * s.uniform()), H - crop);       // RandomCrop: int((H - h + 1) * u)
@@ -215,11 +176,6 @@ __device__ static inline uint8_t fta_mask(const uint8_t* __restrict__ masks, con
     fta_geo(v, S, y, x, sy, sx);
     return masks[((int64_t)b * H + v.y0 + sy) * W + v.x0 + sx];
 }
-__device__ static inline int fta_refl101(int i, int n) {
-    if (n == 1) return 0;
-    while (i < 0 || i >= n) i = i < 0 ? -i : 2 * n - 2 - i;
-    return i;
-}
 
 // ---------------------------------------------------------------------------------------------
 // photometric pass: crop -> GaussNoise -> GaussianBlur (separable, float64 taps in order, float32 after each pass) -> brightness / contrast
@@ -253,7 +209,7 @@ __global__ __launch_bounds__(256) void ftaug_photometric_kernel(const float* __r
     const double sd = (v.ops & FA_NOISE) ? sqrt(rec.var_noise) : 0.0;
     for (int i = threadIdx.x; i < nr * nc; i += 256) {
         const int r = i / nc, c = i % nc;
-        const int y = fta_refl101(ty0 - h + r, S), x = fta_refl101(tx0 - h + c, S);
+        const int y = reflect101(ty0 - h + r, S), x = reflect101(tx0 - h + c, S);
         float a = img[(int64_t)y * W + x];
         if (v.ops & FA_NOISE) {
             const int64_t pix = (int64_t)y * S + x;

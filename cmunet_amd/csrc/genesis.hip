@@ -14,7 +14,7 @@
 //   cmu_mse_fwd_bwd             nn.MSELoss()(logits[:, 0], y) + its gradient, fixed-order reduction
 //
 // Built with -ffp-contract=off (Makefile): every multiply and add of the fp32 control points and of np.interp rounds on its own.
-#include "common.h"
+#include "philox_stream.h"
 #include <math.h>
 
 // ---------------------------------------------------------------------------------------------
@@ -47,55 +47,21 @@ static inline int gen_seg_rows(int H, int W) { return H < GEN_OWNER_WORDS / W ? 
 extern "C" int cmu_genesis_segments(int H, int W) { return W > 0 && W <= GEN_OWNER_WORDS ? cmu_div_up(H, gen_seg_rows(H, W)) : 0; }
 
 // ---------------------------------------------------------------------------------------------
-// Philox streams.  Stream id (c1) = purpose << 28 | image << 14 | block; c0 counts the draws of the stream; (c2, c3) = offset.
+// Philox streams (PhiloxStream, philox_stream.h).  Stream id (c1) = purpose << 28 | image << 14 | block; (c2, c3) = offset.
 // ---------------------------------------------------------------------------------------------
 enum { GS_SELECT = 0, GS_RECORD = 1, GS_BLOCK = 2, GS_NOISE = 3 };
-struct GenStream {
-    uint32_t k0, k1, id, o0, o1, c0;
-    uint32_t buf[4];
-    int pos;
-    __device__ GenStream(uint64_t seed, uint64_t offset, uint32_t id_)
-        : k0((uint32_t)seed), k1((uint32_t)(seed >> 32)), id(id_), o0((uint32_t)offset), o1((uint32_t)(offset >> 32)), c0(0), pos(4) {}
-    __device__ uint32_t next() {
-        if (pos == 4) {
-            philox4x32_10(c0++, id, o0, o1, k0, k1, buf);
-            pos = 0;
-        }
-        return buf[pos++];
-    }
-    // uniform double in [0, 1) on 53 bits, as random.random()
-    __device__ double uniform() {
-        const uint64_t hi = next(), lo = next();
-        return (double)(((hi << 32) | lo) >> 11) * (1.0 / 9007199254740992.0);
-    }
-    // uniform integer in [0, n), n >= 1: Lemire's multiply-shift with rejection (exactly uniform)
-    __device__ uint32_t below(uint32_t n) {
-        uint64_t m = (uint64_t)next() * n;
-        uint32_t l = (uint32_t)m;
-        if (l < n) {
-            const uint32_t t = (0u - n) % n;
-            while (l < t) {
-                m = (uint64_t)next() * n;
-                l = (uint32_t)m;
-            }
-        }
-        return (uint32_t)(m >> 32);
-    }
-    __device__ int randint(int a, int b) { return a + (int)below((uint32_t)(b - a + 1)); }   // random.randint: both ends included
-};
 __device__ static inline uint32_t gen_id(int purpose, int img, int blk) { return ((uint32_t)purpose << 28) | ((uint32_t)img << 14) | (uint32_t)blk; }
 // paint noise of pixel p of image b: float32(np.random.rand()) law
 __device__ static inline float gen_noise(uint64_t seed, uint64_t offset, int b, int64_t p) {
     uint32_t r[4];
     philox4x32_10((uint32_t)p, gen_id(GS_NOISE, b, 0) | (uint32_t)(p >> 32), (uint32_t)offset, (uint32_t)(offset >> 32), (uint32_t)seed,
                   (uint32_t)(seed >> 32), r);
-    const uint64_t u = ((uint64_t)r[0] << 32) | r[1];
-    return (float)((double)(u >> 11) * (1.0 / 9007199254740992.0));
+    return (float)philox_u53(r[0], r[1]);
 }
 
 // data_augmentation's flip loop (`while random.random() < prob and cnt > 0`: the draw comes before the count test) and
 // local_pixel_shuffling's branch -> GF_FLIP0 / GF_FLIP1 / GF_LOCAL bits
-__device__ static inline int gen_flips_local(GenStream& s, double flip_rate, double local_rate) {
+__device__ static inline int gen_flips_local(PhiloxStream& s, double flip_rate, double local_rate) {
     int flags = 0, cnt = 3;
     while (s.uniform() < flip_rate && cnt > 0) {
         flags ^= s.below(2) ? GF_FLIP1 : GF_FLIP0;
@@ -121,14 +87,14 @@ __global__ __launch_bounds__(256) void genesis_sample_kernel(GenesisRec* __restr
     const int slot = (H / 25) * (W / 25);
     if (threadIdx.x == 0 && blockIdx.y != 0) {
         // the other slices of the image only need the local-shuffle decision: replay the record stream up to it
-        GenStream s(seed, offset, gen_id(GS_RECORD, b, 0));
+        PhiloxStream s(seed, offset, gen_id(GS_RECORD, b, 0));
         local = mae ? 0 : gen_flips_local(s, flip_rate, local_rate) & GF_LOCAL;
     }
     if (threadIdx.x == 0 && blockIdx.y == 0) {
         GenesisRec r = {};
         // batch selection: random.shuffle(index)[:B] is a uniformly random ordered sample without replacement -- sequential
         // rejection sampling has the same law (every image's workgroup replays the draws up to its own position)
-        GenStream sel(seed, offset, gen_id(GS_SELECT, 0, 0));
+        PhiloxStream sel(seed, offset, gen_id(GS_SELECT, 0, 0));
         for (int i = 0; i <= b; ++i) {
             int j;
             bool dup;
@@ -144,7 +110,7 @@ __global__ __launch_bounds__(256) void genesis_sample_kernel(GenesisRec* __restr
         r.block_off = (int64_t)b * GEN_NBLOCKS;
         r.perm_off = (int64_t)b * GEN_NBLOCKS * slot;
         if (!mae) {
-            GenStream s(seed, offset, gen_id(GS_RECORD, b, 0));
+            PhiloxStream s(seed, offset, gen_id(GS_RECORD, b, 0));
             r.flags = gen_flips_local(s, flip_rate, local_rate);
             if (r.flags & GF_LOCAL) r.nblocks = GEN_NBLOCKS;
             int cnt;
@@ -191,7 +157,7 @@ __global__ __launch_bounds__(256) void genesis_sample_kernel(GenesisRec* __restr
     uint8_t* sc = scratch[threadIdx.x];
     const int per = (GEN_NBLOCKS + gridDim.y - 1) / gridDim.y, k1 = min(GEN_NBLOCKS, (int)(blockIdx.y + 1) * per);
     for (int k = blockIdx.y * per + threadIdx.x; k < k1; k += 256) {
-        GenStream s(seed, offset, gen_id(GS_BLOCK, b, k));
+        PhiloxStream s(seed, offset, gen_id(GS_BLOCK, b, k));
         const int bx = s.randint(1, H / 25), by = s.randint(1, W / 25);
         const int x0 = s.randint(0, H - bx), y0 = s.randint(0, W - by);
         int16_t* q = blocks + ((int64_t)b * GEN_NBLOCKS + k) * 4;

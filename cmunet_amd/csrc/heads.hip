@@ -2,36 +2,9 @@
 //   masked reconstruction loss (cmunet_head.py:62-70), finetune softmax-CE + Dice/IoU counters
 //   (metrics.py:135-180,503), in-batch InfoNCE (cmunet_head.py:72-88), MoCo InfoNCE + queue update in
 //   one launch (moco2_module.py:160-175,256-285), L2 row normalisation, EMA and Adam over flat arenas.
-// These are latency/HBM-bound: one pass per tensor, wave64 shuffle reductions, fixed-order final sums.
+// These are latency/HBM-bound: one pass per tensor, wave64 shuffle reductions (block_sum / block_sum_d / block_max, common.h),
+// fixed-order final sums.
 #include "common.h"
-
-__device__ static inline float block_sum(float v, float* red /*[4]*/) {
-    v = wave_sum(v);
-    __syncthreads();
-    if ((threadIdx.x & 63) == 0) red[threadIdx.x >> 6] = v;
-    __syncthreads();
-    float a = 0.f;
-    for (int i = 0; i < (int)(blockDim.x >> 6); ++i) a += red[i];
-    return a;
-}
-__device__ static inline double block_sum_d(double v, double* red /*[4]*/) {
-    v = wave_sum_d(v);
-    __syncthreads();
-    if ((threadIdx.x & 63) == 0) red[threadIdx.x >> 6] = v;
-    __syncthreads();
-    double a = 0.0;
-    for (int i = 0; i < (int)(blockDim.x >> 6); ++i) a += red[i];
-    return a;
-}
-__device__ static inline float block_max(float v, float* red /*[4]*/) {
-    v = wave_max(v);
-    __syncthreads();
-    if ((threadIdx.x & 63) == 0) red[threadIdx.x >> 6] = v;
-    __syncthreads();
-    float a = red[0];
-    for (int i = 1; i < (int)(blockDim.x >> 6); ++i) a = fmaxf(a, red[i]);
-    return a;
-}
 
 // ---------------------------------------------------------------------------------------------
 // masked MSE: ws = [rows][4] floats (mean, rstd, num, den) + [2] (loss, den_total)
@@ -224,7 +197,6 @@ extern "C" int cmu_masked_mse_fwd_bwd(const float* logits, int K, int channel, c
 // softmax CE (probability targets) + Dice / IoU counters, 2 classes
 // ws: [blocks][4] doubles (ce, tp, sum_pr, sum_gt)
 // ---------------------------------------------------------------------------------------------
-constexpr int CE_MAX_BLOCKS = 1024;
 __global__ __launch_bounds__(256) void ce_dice_kernel(const float* __restrict__ logits, const double* __restrict__ y1h,
                                                      double* __restrict__ ws, float* __restrict__ dlogits, float gscale, int64_t HW,
                                                      int64_t npix) {

@@ -70,20 +70,6 @@ __device__ static inline void moco_grid_barrier(unsigned* counter, unsigned targ
     __threadfence();   // every wave: what the other workgroups wrote before the barrier is visible to its loads
 }
 
-__device__ static inline float moco_block_sum(float v, float* red) {
-    v = wave_sum(v);
-    __syncthreads();
-    if ((threadIdx.x & 63) == 0) red[threadIdx.x >> 6] = v;
-    __syncthreads();
-    return (red[0] + red[1]) + (red[2] + red[3]);
-}
-__device__ static inline float moco_block_max(float v, float* red) {
-    v = wave_max(v);
-    __syncthreads();
-    if ((threadIdx.x & 63) == 0) red[threadIdx.x >> 6] = v;
-    __syncthreads();
-    return fmaxf(fmaxf(red[0], red[1]), fmaxf(red[2], red[3]));
-}
 __device__ static inline f32x4m moco_ld4(const float* p, bool ok) {
     return ok ? *reinterpret_cast<const f32x4m*>(p) : f32x4m{0.f, 0.f, 0.f, 0.f};
 }
@@ -108,8 +94,8 @@ __global__ __launch_bounds__(256) void moco_fused_kernel(const MocoParams p) {
             s = fmaf(q[d], q[d], s);
             s2 = fmaf(kk[d], kk[d], s2);
         }
-        const float qnorm = fmaxf(sqrtf(moco_block_sum(s, red4)), 1e-12f);
-        const float knorm = fmaxf(sqrtf(moco_block_sum(s2, red4)), 1e-12f);
+        const float qnorm = fmaxf(sqrtf(block_sum4(s, red4)), 1e-12f);
+        const float knorm = fmaxf(sqrtf(block_sum4(s2, red4)), 1e-12f);
         float pos = 0.f;
         for (int d = tid; d < D; d += 256) {
             const float a = q[d] / qnorm, k_ = kk[d] / knorm;
@@ -119,7 +105,7 @@ __global__ __launch_bounds__(256) void moco_fused_kernel(const MocoParams p) {
             if (p.k_norm_out) p.k_norm_out[(int64_t)b * D + d] = k_;
             pos = fmaf(a, k_, pos);
         }
-        pos = moco_block_sum(pos, red4) / p.temp;
+        pos = block_sum4(pos, red4) / p.temp;
         if (tid == 0) {
             p.rowst[b * 4 + 0] = qnorm;
             p.rowst[b * 4 + 1] = pos;
@@ -190,10 +176,10 @@ __global__ __launch_bounds__(256) void moco_fused_kernel(const MocoParams p) {
         const float pos = p.rowst[b * 4 + 1];
         float m = pos;
         for (int j = tid; j < K; j += 256) m = fmaxf(m, Lr[j]);
-        m = moco_block_max(m, red4);
+        m = block_max4(m, red4);
         float se = 0.f;
         for (int j = tid; j < K; j += 256) se += expf(Lr[j] - m);
-        se = moco_block_sum(se, red4) + expf(pos - m);
+        se = block_sum4(se, red4) + expf(pos - m);
         const float inv = 1.f / (se * (float)B * p.temp);
         for (int j = tid; j < K; j += 256) Lr[j] = expf(Lr[j] - m) * inv;
         if (tid == 0) {
@@ -264,7 +250,7 @@ __global__ __launch_bounds__(256) void moco_fused_kernel(const MocoParams p) {
                 p.dq[(int64_t)b * D + d] = g;                       // (dqn; finished below)
                 dot = fmaf(g, p.qn[(int64_t)b * D + d], dot);
             }
-            dot = moco_block_sum(dot, red4);
+            dot = block_sum4(dot, red4);
             for (int d = tid; d < D; d += 256) p.dq[(int64_t)b * D + d] = (p.dq[(int64_t)b * D + d] - p.qn[(int64_t)b * D + d] * dot) / qnorm;
         }
     }

@@ -15,7 +15,7 @@
 //
 // Built with -ffp-contract=off (Makefile): the nearest-neighbour index and the resize's source coordinates are torch's float32 arithmetic,
 // operation by operation.
-#include "common.h"
+#include "philox_stream.h"
 #include <math.h>
 #include <stddef.h>
 #pragma clang fp contract(off)
@@ -37,47 +37,11 @@ extern "C" int cmu_mocoviews_rec_layout(int64_t* out, int n) {
                          (int64_t)offsetof(CmuMocoViewRec, left), (int64_t)offsetof(CmuMocoViewRec, height),
                          (int64_t)offsetof(CmuMocoViewRec, width), (int64_t)offsetof(CmuMocoViewRec, angle),
                          (int64_t)offsetof(CmuMocoViewRec, sigma)};
-    const int m = (int)(sizeof(v) / sizeof(v[0]));
-    for (int i = 0; i < m && i < n; ++i) out[i] = v[i];
-    return m;
+    return cmu_export_layout(v, out, n);
 }
 
-// ---------------------------------------------------------------------------------------------
-// randomness.  Record stream: c0 counts the draws, c1 = purpose << 28 | record, (c2, c3) = offset, key = seed.  Pixel noise: c0 = group of
-// four pixels of the view, c1 = purpose << 28 | record; two Box-Muller pairs on 24-bit uniforms in (0, 1).
-// ---------------------------------------------------------------------------------------------
-__device__ static inline uint32_t mv_id(int purpose, int rec) { return ((uint32_t)purpose << 28) | (uint32_t)rec; }
-struct MvStream {
-    uint32_t k0, k1, id, o0, o1, c0;
-    uint32_t buf[4];
-    int pos;
-    __device__ MvStream(uint64_t seed, uint64_t offset, uint32_t id_)
-        : k0((uint32_t)seed), k1((uint32_t)(seed >> 32)), id(id_), o0((uint32_t)offset), o1((uint32_t)(offset >> 32)), c0(0), pos(4) {}
-    __device__ uint32_t next() {
-        if (pos == 4) {
-            philox4x32_10(c0++, id, o0, o1, k0, k1, buf);
-            pos = 0;
-        }
-        return buf[pos++];
-    }
-    __device__ double uniform() {                                   // [0, 1), 53 bits
-        const uint64_t hi = next(), lo = next();
-        return (double)(((hi << 32) | lo) >> 11) * (1.0 / 9007199254740992.0);
-    }
-    __device__ double uniform(double a, double b) { return __dadd_rn(a, __dmul_rn(__dadd_rn(b, -a), uniform())); }
-    __device__ uint32_t below(uint32_t n) {                         // uniform integer in [0, n): Lemire's multiply-shift with rejection
-        uint64_t m = (uint64_t)next() * n;
-        uint32_t l = (uint32_t)m;
-        if (l < n) {
-            const uint32_t t = (0u - n) % n;
-            while (l < t) {
-                m = (uint64_t)next() * n;
-                l = (uint32_t)m;
-            }
-        }
-        return (uint32_t)(m >> 32);
-    }
-};
+// randomness.  Record stream (PhiloxStream, philox_stream.h): c1 = purpose << 28 | record, (c2, c3) = offset, key = seed.  Pixel noise:
+// c0 = group of four pixels of the view, c1 = purpose << 28 | record; two Box-Muller pairs on 24-bit uniforms in (0, 1).
 
 // ---------------------------------------------------------------------------------------------
 // sampler: every draw is made whether or not its transform fires (all ten crop attempts included), so each parameter sits at a fixed
@@ -91,7 +55,7 @@ __global__ __launch_bounds__(64) void mocoviews_sample_kernel(CmuMocoViewRec* __
     const int i = blockIdx.x * 64 + threadIdx.x;
     if (i >= n) return;
     const double* p = P.p;
-    MvStream s(seed, offset, mv_id(MVS_RECORD, i));
+    PhiloxStream s(seed, offset, philox_id(MVS_RECORD, i));
     CmuMocoViewRec r;
     r.ops = 0;
     r.pad = 0;
@@ -164,11 +128,6 @@ __device__ static inline uint32_t mv_ord(float f) {
     return (u & 0x80000000u) ? ~u : (u | 0x80000000u);
 }
 __device__ static inline float mv_unord(uint32_t u) { return __uint_as_float((u & 0x80000000u) ? (u & 0x7fffffffu) : ~u); }
-__device__ static inline int mv_reflect(int i, int n) {            // reflect padding without edge repeat
-    if (n == 1) return 0;
-    while (i < 0 || i >= n) i = i < 0 ? -i : 2 * n - 2 - i;
-    return i;
-}
 // one output index of the resize crop-side n -> O: the first source index, the tap count and the weights
 struct MvTaps {
     int start, count;
@@ -258,8 +217,8 @@ __global__ __launch_bounds__(256) void mocoviews_geometry_kernel(const float* __
         R.y0 = __fadd_rn(__fmul_rn(-(float)H, 0.5f), 0.5f);
     }
     const int tid = threadIdx.x;
-    if (tid < nr) mv_taps(trow[tid], mv_reflect(ty0 - hy + tid, O), ch, O, antialias);
-    if (tid >= 64 && tid - 64 < nc) mv_taps(tcol[tid - 64], mv_reflect(tx0 - hx + tid - 64, O), cw, O, antialias);
+    if (tid < nr) mv_taps(trow[tid], reflect101(ty0 - hy + tid, O), ch, O, antialias);
+    if (tid >= 64 && tid - 64 < nc) mv_taps(tcol[tid - 64], reflect101(tx0 - hx + tid - 64, O), cw, O, antialias);
     if (blur && tid >= 128 && tid < 130) {
         // _get_gaussian_kernel1d: exp(-0.5 (x / sigma)^2) over linspace(-(k-1)/2, (k-1)/2, k), divided by its sum (float32)
         const int k = tid == 128 ? kx : ky;
@@ -377,7 +336,7 @@ __global__ __launch_bounds__(256) void mocoviews_noise_kernel(float* __restrict_
         for (int j = 0; j < cnt; ++j) z[j] = noise[base + p0 + j];
     } else {
         uint32_t r[4];
-        philox4x32_10((uint32_t)g, mv_id(MVS_NOISE, ri), (uint32_t)offset, (uint32_t)(offset >> 32), (uint32_t)seed, (uint32_t)(seed >> 32), r);
+        philox4x32_10((uint32_t)g, philox_id(MVS_NOISE, ri), (uint32_t)offset, (uint32_t)(offset >> 32), (uint32_t)seed, (uint32_t)(seed >> 32), r);
         for (int j = 0; j < 2; ++j) {
             const float u1 = ((float)(r[2 * j] >> 8) + 0.5f) * (1.f / 16777216.f), u2 = ((float)(r[2 * j + 1] >> 8) + 0.5f) * (1.f / 16777216.f);
             const float rad = sqrtf(-2.f * logf(u1));

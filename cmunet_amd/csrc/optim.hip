@@ -80,14 +80,6 @@ extern "C" int cmu_sgd_step_amp(float* p, const float* g, float* buf, const uint
 // ---------------------------------------------------------------------------------------------
 constexpr int LAMB_BLK = 4096;
 
-__device__ static inline float block_sum_256(float v, float* red) {
-    v = wave_sum(v);
-    __syncthreads();
-    if ((threadIdx.x & 63) == 0) red[threadIdx.x >> 6] = v;
-    __syncthreads();
-    return (red[0] + red[1]) + (red[2] + red[3]);
-}
-
 __global__ __launch_bounds__(256) void lamb_gradsq_kernel(const float* __restrict__ g, const int64_t* __restrict__ blk_start,
                                                          const int* __restrict__ blk_count, float gscale, float* __restrict__ part) {
     __shared__ float red[4];
@@ -98,7 +90,7 @@ __global__ __launch_bounds__(256) void lamb_gradsq_kernel(const float* __restric
         const float gi = g[s + i] * gscale;
         a = fmaf(gi, gi, a);
     }
-    a = block_sum_256(a, red);
+    a = block_sum4(a, red);
     if (threadIdx.x == 0) part[blockIdx.x] = a;
 }
 __global__ __launch_bounds__(256) void lamb_gnorm_kernel(const float* __restrict__ part, int nblocks, float max_norm, float* __restrict__ scal) {
@@ -142,8 +134,8 @@ __global__ __launch_bounds__(256) void lamb_update_kernel(const float* __restric
         sp = fmaf(pi, pi, sp);
         su = fmaf(up, up, su);
     }
-    sp = block_sum_256(sp, red);
-    su = block_sum_256(su, red);
+    sp = block_sum4(sp, red);
+    su = block_sum4(su, red);
     if (threadIdx.x == 0) {
         part2[2 * (int64_t)blockIdx.x + 0] = sp;
         part2[2 * (int64_t)blockIdx.x + 1] = su;

@@ -7,19 +7,9 @@
 // device memory (no host synchronisation anywhere).
 #include "common.h"
 
-constexpr int CE_MAX_BLOCKS = 1024;      // as heads.hip
 constexpr int PWL_MAX_C = 8;             // channels of the per-channel weight vectors; classes of the index CE
 static_assert(PWL_MAX_C == CMU_PWL_MAX_C, "header constant");
 
-__device__ static inline double block_sum_d(double v, double* red /*[4]*/) {
-    v = wave_sum_d(v);
-    __syncthreads();
-    if ((threadIdx.x & 63) == 0) red[threadIdx.x >> 6] = v;
-    __syncthreads();
-    double a = 0.0;
-    for (int i = 0; i < (int)(blockDim.x >> 6); ++i) a += red[i];
-    return a;
-}
 template <typename T, int V>
 struct alignas(sizeof(T) * V < 16 ? sizeof(T) * V : 16) PwVec {
     T v[V];

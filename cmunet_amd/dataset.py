@@ -9,10 +9,35 @@ the reference, plus the synthetic generators used by bench.py and the tests (the
   CMUNetDataset(data_root, data_ann, pipeline, pixel=31, test=False)   cmae/datasets/cmunet_dataset.py:16-88: directory of ``.npy``
       images, the reference's two train_test_split calls, items {'img','img_t'} built by ``two_view_item``.
   MoCoDataset(data_path, tau_g)                                         moco/moco_data_set.py:11-37: item ((crop_0, crop_1), 0).
+  epoch_permutation, apply_overrides, check_probabilities               shared by the device loaders and the sampler configs
+      (ft_augment.py, moco_views.py, genesis.py).
 """
 import numpy as np
 import torch
 from torch.utils.data import Dataset
+
+
+def epoch_permutation(n, seed, epoch, device):
+    """The order of epoch ``epoch`` of a device loader seeded with ``seed``: a uniform permutation of range(n) on ``device``."""
+    g = torch.Generator(device=device)
+    g.manual_seed((seed * 1000003 + epoch) & (2 ** 63 - 1))
+    # argsort of uniform keys drawn on the device: a uniform permutation without a host round trip
+    return torch.argsort(torch.rand(n, generator=g, device=device))
+
+
+def apply_overrides(config, kw):
+    """Keyword overrides of a config object whose defaults are set: a name it does not have is a TypeError."""
+    for k, v in kw.items():
+        if not hasattr(config, k):
+            raise TypeError(f"{type(config).__name__}: unknown setting {k!r}")
+        setattr(config, k, v)
+
+
+def check_probabilities(config, names):
+    for name in names:
+        p = float(getattr(config, name))
+        if not 0.0 <= p <= 1.0:
+            raise ValueError(f"{name} = {p} is not a probability")
 
 
 def one_hot_encode(label, label_values):

@@ -26,6 +26,7 @@ import torch
 
 from . import _lib, ops
 from ._lib import call
+from .dataset import apply_overrides, check_probabilities, epoch_permutation
 
 OP_NOISE, OP_BLUR, OP_BRIGHTNESS_CONTRAST, OP_DOWNSCALE, OP_ONEOF = 1, 2, 4, 8, 16
 ONEOF_HFLIP, ONEOF_VFLIP, ONEOF_ROT90, ONEOF_NOISE = 0, 1, 2, 3
@@ -68,10 +69,7 @@ class FinetuneAugmentConfig:
         self.p_oneof = 0.75                     # OneOf([HorizontalFlip, VerticalFlip, RandomRotate90, GaussNoise()], p=0.75)
         self.oneof_var_limit = (10.0, 50.0)     # GaussNoise()'s default var_limit
         self.clip_float = True
-        for k, v in kw.items():
-            if not hasattr(self, k):
-                raise TypeError(f"FinetuneAugmentConfig: unknown setting {k!r}")
-            setattr(self, k, v)
+        apply_overrides(self, kw)
         klo, khi = (3, int(self.blur_limit)) if np.isscalar(self.blur_limit) else (int(v) for v in self.blur_limit)
         if not (1 <= klo <= khi) or khi % 2 != 1:
             raise ValueError(f"blur_limit {self.blur_limit}: needs 1 <= low <= high with an odd high")
@@ -79,10 +77,7 @@ class FinetuneAugmentConfig:
             raise ValueError(f"blur_limit {self.blur_limit}: kernel sizes above {MAX_KSIZE} are not supported (the compile-time maximum "
                              "of the photometric pass's LDS halo)")
         self.blur_limit = (klo, khi)
-        for name in ("p_noise", "p_blur", "p_brightness_contrast", "p_downscale", "p_oneof"):
-            p = float(getattr(self, name))
-            if not 0.0 <= p <= 1.0:
-                raise ValueError(f"{name} = {p} is not a probability")
+        check_probabilities(self, ("p_noise", "p_blur", "p_brightness_contrast", "p_downscale", "p_oneof"))
         if int(self.crop) <= 0:
             raise ValueError("crop must be positive")
         if not 0.0 < _pair(self.scale_limit)[0] <= _pair(self.scale_limit)[1] <= 1.0:
@@ -278,10 +273,7 @@ class _DeviceLoader:
         n = len(self.idx)
         order = self.idx
         if self.shuffle:
-            g = torch.Generator(device=self.images.device)
-            g.manual_seed((self.seed * 1000003 + self.epoch) & (2 ** 63 - 1))
-            # argsort of uniform keys drawn on the device: a uniform permutation without a host round trip
-            order = self.idx.index_select(0, torch.argsort(torch.rand(n, generator=g, device=self.images.device)))
+            order = self.idx.index_select(0, epoch_permutation(n, self.seed, self.epoch, self.images.device))
         self.epoch += 1
         for j in range(0, n, self.batch_size):
             sel = order[j:j + self.batch_size]

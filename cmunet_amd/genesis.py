@@ -22,6 +22,7 @@ import torch
 
 from . import _lib, ops
 from ._lib import call
+from .dataset import apply_overrides
 from .optim import FlatParams, FusedSGD
 from .pretrain import ArenaTrainer, create_random_patch_mask, default_amp, dp_exchanges
 
@@ -62,10 +63,7 @@ class GenesisConfig:
         self.flip_rate = 0.4
         self.model_path = "pretrained_weights"
         exp_name = kw.pop("exp_name", None)
-        for k, v in kw.items():
-            if not hasattr(self, k):
-                raise TypeError(f"GenesisConfig: unknown setting {k!r}")
-            setattr(self, k, v)
+        apply_overrides(self, kw)
         self.inpaint_rate = 1.0 - self.outpaint_rate
         self.exp_name = exp_name or f"{self.model}-{self.suffix}"
         if self.model not in ("Model Genesis", "MAE"):

@@ -23,6 +23,7 @@ import torch
 
 from . import _lib, ops
 from ._lib import call
+from .dataset import apply_overrides, check_probabilities, epoch_permutation
 
 OP_ROTATION, OP_BLUR, OP_HFLIP, OP_VFLIP, OP_NOISE = 1, 2, 4, 8, 16
 
@@ -62,14 +63,8 @@ class MocoViewConfig:
         self.size = 256
         self.out = 224
         self.antialias = False
-        for k, v in kw.items():
-            if not hasattr(self, k):
-                raise TypeError(f"MocoViewConfig: unknown setting {k!r}")
-            setattr(self, k, v)
-        for name in ("p_rotation", "p_blur", "p_hflip", "p_vflip", "p_noise"):
-            p = float(getattr(self, name))
-            if not 0.0 <= p <= 1.0:
-                raise ValueError(f"{name} = {p} is not a probability")
+        apply_overrides(self, kw)
+        check_probabilities(self, ("p_rotation", "p_blur", "p_hflip", "p_vflip", "p_noise"))
         ks = (int(self.kernel_size),) * 2 if np.isscalar(self.kernel_size) else tuple(int(v) for v in self.kernel_size)
         if len(ks) != 2 or any(k < 1 or k % 2 != 1 for k in ks):
             raise ValueError(f"kernel_size {self.kernel_size}: needs two odd positive sizes (x, y)")
@@ -246,13 +241,9 @@ class _ViewLoader:
         return n // self.batch_size if self.drop_last else (n + self.batch_size - 1) // self.batch_size
 
     def __iter__(self):
-        n, dev = self.images.shape[0], self.images.device
         order = self.idx
         if self.shuffle:
-            g = torch.Generator(device=dev)
-            g.manual_seed((self.seed * 1000003 + self.epoch) & (2 ** 63 - 1))
-            # argsort of uniform keys drawn on the device: a uniform permutation without a host round trip
-            order = torch.argsort(torch.rand(n, generator=g, device=dev))
+            order = epoch_permutation(len(order), self.seed, self.epoch, order.device)
         self.last_order = order
         self.epoch += 1
         for k in range(len(self)):

@@ -82,6 +82,11 @@ def test_config_refusals():
         FA.FinetuneAugmentConfig(p_noise=1.5)
     with pytest.raises(TypeError, match="unknown"):
         FA.FinetuneAugmentConfig(crop_width=400)
+    # the whole messages (the override and probability helpers are shared with the other sampler configs)
+    with pytest.raises(TypeError, match=r"^FinetuneAugmentConfig: unknown setting 'crop_width'$"):
+        FA.FinetuneAugmentConfig(crop_width=400)
+    with pytest.raises(ValueError, match=r"^p_oneof = -0\.25 is not a probability$"):
+        FA.FinetuneAugmentConfig(p_oneof=-0.25)
 
 
 def test_record_dtype_matches_the_c_struct():

@@ -94,6 +94,9 @@ def test_config_defaults_and_refusals():
         G.GenesisConfig(model="SimCLR")
     with pytest.raises(ValueError):
         G.GenesisConfig(optimizer="adam")
+    assert G.GenesisConfig(flip_rate=0.25, exp_name="x").flip_rate == 0.25
+    with pytest.raises(TypeError, match=r"^GenesisConfig: unknown setting 'flip_prob'$"):
+        G.GenesisConfig(flip_prob=0.25)
 
 
 def _unet_shapes():

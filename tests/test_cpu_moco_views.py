@@ -114,6 +114,11 @@ def test_config_defaults_and_validation():
     assert list(c.params()) == [0.5, 180.0, 0.2, 1.0, 0.75, 4.0 / 3.0, 0.5, 0.1, 2.0, 0.5, 0.5, 0.5]
     with pytest.raises(TypeError, match="unknown setting"):
         MV.MocoViewConfig(p_rotate=0.5)
+    # the whole messages (the override and probability helpers are shared with the other sampler configs)
+    with pytest.raises(TypeError, match=r"^MocoViewConfig: unknown setting 'p_rotate'$"):
+        MV.MocoViewConfig(p_rotate=0.5)
+    with pytest.raises(ValueError, match=r"^p_blur = 1\.5 is not a probability$"):
+        MV.MocoViewConfig(p_blur=1.5)
     for bad in (dict(p_blur=1.5), dict(kernel_size=(4, 9)), dict(scale=(0.0, 1.0)), dict(sigma=(2.0, 0.1)), dict(ratio=(2.0, 1.0)),
                 dict(degrees=-1), dict(out=2), dict(antialias=True, size=512, out=224)):
         with pytest.raises(ValueError):

@@ -35,6 +35,27 @@ def test_segmentation_dataset_contract(tmp_path):
     assert it["img"].shape == it["img_t"].shape == (224, 224) and it["img"].dtype == np.float32   # cmunet_dataset.py:60-88
 
 
+def test_epoch_permutation_is_the_loaders_arithmetic():
+    """The shuffle of both device loaders (ft_augment._DeviceLoader, moco_views._ViewLoader): argsort of uniform keys from a generator
+    seeded with (seed * 1000003 + epoch) & (2**63 - 1), the arithmetic the two loaders used to carry separately."""
+    from cmunet_amd.dataset import epoch_permutation
+    n, seed, epoch = 37, 5, 3
+    idx = torch.arange(100, 100 + n)
+    order = epoch_permutation(n, seed, epoch, "cpu")
+    assert order.dtype == torch.int64 and order.shape == (n,)
+    assert torch.equal(torch.sort(order).values, torch.arange(n))
+    assert torch.equal(torch.sort(idx.index_select(0, order)).values, idx)       # a permutation of the given indices
+    assert torch.equal(order, epoch_permutation(n, seed, epoch, "cpu"))           # same (seed, epoch): same order
+    assert not torch.equal(order, epoch_permutation(n, seed, epoch + 1, "cpu"))   # the next epoch: another one
+    assert not torch.equal(order, epoch_permutation(n, seed + 1, epoch, "cpu"))
+    g = torch.Generator(device="cpu")
+    g.manual_seed((seed * 1000003 + epoch) & (2 ** 63 - 1))
+    assert torch.equal(order, torch.argsort(torch.rand(n, generator=g, device="cpu")))
+    big = 2 ** 62 + 12345                                                        # the mask keeps the seed in manual_seed's range
+    g.manual_seed((big * 1000003 + epoch) & (2 ** 63 - 1))
+    assert torch.equal(epoch_permutation(n, big, epoch, "cpu"), torch.argsort(torch.rand(n, generator=g, device="cpu")))
+
+
 def test_load_model_checkpoint_layouts(tmp_path, golden_dir):
     """Synthetic checkpoints in each of the five foreign layouts -> the keys that must land in UNet(): exactly the keys the
     REFERENCE's own load_model loaded from the same files (tests/golden/load_model_ref.npz, oracle/gen_golden.py::gen_load_model)."""
