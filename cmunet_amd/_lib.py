@@ -216,6 +216,14 @@ _SIGS = {
     "cmu_select_largest": (_I, [_P, _I, _P, _I, _I, _I, _P]),
     "cmu_border_components": (_I, [_P, _P, _I, _I, _I, _P]),
     "cmu_filter_components": (_I, [_P, _I, _P, _P, _I, _P, _I, _I, _P, _P, _P, _I, _P, _I, _I, _I, _P]),
+    "cmu_pre_stats": (_I, [_P, _I, _P, _I, _I, _I, _P]),
+    "cmu_pre_standardize": (_I, [_P, _I, _P, _P, _I, _I, _I, _P]),
+    "cmu_pre_minmax": (_I, [_P, _I, _P, _P, _I, _I, _I, _P]),
+    "cmu_pre_row_normalize": (_I, [_P, _I, _P, _I, _I, _I, _P]),
+    "cmu_pre_blur_rows": (_I, [_P, _I, _F, _P, _I, _P, _I, _I, _I, _P]),
+    "cmu_pre_unsharp_cols": (_I, [_P, _I, _F, _P, _P, _I, _F, _I, _P, _P, _I, _I, _I, _P]),
+    "cmu_pre_crop": (_I, [_P, _I, _P, _I, _I, _I, _I, _I, _I, _I, _P]),
+    "cmu_pre_integrate_masks": (_I, [_P, _P, _I, _I, _L, _P]),
     "cmu_amp_state_bytes": (_I, []),
     "cmu_amp_init": (_I, [_P, _F, _P]),
     "cmu_amp_check_finite": (_I, [_P, _L, _P, _P]),

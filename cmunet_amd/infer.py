@@ -6,6 +6,7 @@
   python -m cmunet_amd.infer --model M --images DIR --out DIR [--size 256] [--batch 32] [--dtype f16] [--threshold 0.5]
                               [--tile 256 [--stride 128] [--window gaussian] [--pad reflect]] [--tta d4]
                               [--min-size 50] [--keep-largest 2] [--fill-holes] [--connectivity 8]
+                              [--crop 475] [--unsharp RADIUS AMOUNT [--preserve-range]] [--normalize {none,intensity,minmax,rows}]
 
 Per chunk of same-sized images: the training pipeline's resize (``ops.resize_bicubic``: Pillow's bicubic in the image's own
 arithmetic, mode 'F' for float32 / mode 'L' for uint8, as ``dataset.DeviceSegmentationBatch`` feeds finetuning) -> ``UNet.predict``
@@ -16,6 +17,10 @@ With ``tile`` and / or ``tta`` the chunk runs the tiled path instead (csrc/tiled
 windows (in every flip / rotation asked for) out of the padded image, ``UNet.predict_probs`` writes every class's probability of each
 tile back in the image's frame, ``ops.blend_tiles`` sums them under a window in a fixed order and takes the argmax / threshold.
 ``size=None`` then means the image's own resolution, whatever its size.
+
+With ``preprocess`` (a callable such as ``preprocess.Preprocess``: the reference's data_processing steps, csrc/preprocess.hip) every
+device chunk of raw images passes through it first, so raw image -> mask is one call that never leaves the device; the masks then have
+the PREPROCESSED size (the cropped one).
 """
 import argparse
 import os
@@ -24,6 +29,7 @@ import numpy as np
 import torch
 
 from . import ops, postprocess
+from . import preprocess as _preprocess
 from .model import UNet, _EngineOwner, class_value_table
 
 
@@ -128,10 +134,15 @@ class Segmenter:
     ``postprocess.clean_mask`` runs on every mask AT THE IMAGE'S OWN SIZE (after the nearest-neighbour resize back, so ``min_size``
     counts source pixels), on the plain and the tiled path, for every class but 0: components (``connectivity`` 4 or 8) of fewer
     than ``min_size`` pixels are removed, then only the ``keep_largest`` (1..8) largest stay, then holes are filled.  The network and
-    blend passes then write class indices and the clean-up's last pass applies ``class_values``.  ``prob`` outputs are untouched."""
+    blend passes then write class indices and the clean-up's last pass applies ``class_values``.  ``prob`` outputs are untouched.
+
+    ``preprocess`` (None: the calls above run exactly as before): a callable ``(n,H,W) uint8 / float32 device batch -> (n,H',W')`` --
+    ``preprocess.Preprocess`` -- applied to every chunk before the resize / tiling.  Masks (and ``min_size``) are then at the
+    preprocessed size H' x W', e.g. the cropped one, not the raw image's; the ``size=None`` multiple-of-2**(depth-1) rule applies to
+    H' x W'."""
 
     def __init__(self, model, size=256, batch=32, threshold=0.5, class_values=None, tile=None, stride=None, window="gaussian",
-                 pad="reflect", tta=None, min_size=None, keep_largest=None, fill_holes=False, connectivity=8):
+                 pad="reflect", tta=None, min_size=None, keep_largest=None, fill_holes=False, connectivity=8, preprocess=None):
         self.model, self.size, self.batch, self.threshold = model, size, int(batch), threshold
         self.mult = 1 << (_depth(model) - 1)
         if size is not None and (int(size) <= 0 or int(size) % self.mult):
@@ -180,6 +191,9 @@ class Segmenter:
         self.keep_largest = None if keep_largest is None else int(keep_largest)
         self.fill_holes, self.connectivity = fill_holes, connectivity
         self.post = self.min_size is not None or self.keep_largest is not None or self.fill_holes
+        if preprocess is not None and not callable(preprocess):
+            raise ValueError(f"Segmenter: preprocess must be None or a callable, got {type(preprocess).__name__}")
+        self.preprocess = preprocess
 
     def _table(self, device, head=True):
         """The class-value table; ``head``: for the prediction head / the blend, which write class indices when the mask is cleaned
@@ -265,7 +279,7 @@ class Segmenter:
                 raise ValueError(f"Segmenter: every image must be 2-D, got {tuple(t.shape)}")
             if t.dtype != torch.uint8:
                 t = t.float()
-            if self.size is None and self.tile is None and (t.shape[0] % self.mult or t.shape[1] % self.mult):
+            if self.preprocess is None and self.size is None and self.tile is None and (t.shape[0] % self.mult or t.shape[1] % self.mult):
                 raise ValueError(f"Segmenter(size=None): image {tuple(t.shape)} is not a multiple of {self.mult}")
             items.append(t)
         groups = {}
@@ -276,6 +290,13 @@ class Segmenter:
             for c0 in range(0, len(idx), self.batch):
                 part = idx[c0:c0 + self.batch]
                 src = torch.stack([items[i].to(dev, non_blocking=True) for i in part]).contiguous()
+                if self.preprocess is not None:
+                    src = self.preprocess(src)
+                    if src.dim() != 3 or src.shape[0] != len(part) or src.dtype not in (torch.uint8, torch.float32):
+                        raise ValueError(f"Segmenter: preprocess must return (n,H,W) uint8 / float32, got {tuple(src.shape)} {src.dtype}")
+                    if self.size is None and self.tile is None and (src.shape[1] % self.mult or src.shape[2] % self.mult):
+                        raise ValueError(f"Segmenter(size=None): preprocessed image {tuple(src.shape[1:])} is not a multiple of {self.mult}")
+                    src = src.contiguous()
                 res = self._chunk(src, prob_class)
                 for j, i in enumerate(part):
                     out[i] = res[j] if prob_class is None else (res[0][j], res[1][j])
@@ -300,7 +321,7 @@ def segment_files(model, paths, out_dir, **kw):
     return written
 
 
-def main(argv=None):
+def build_parser():
     ap = argparse.ArgumentParser(prog="python -m cmunet_amd.infer", description="Segment .npy images with a finetuned UNet on the GPU.")
     ap.add_argument("--model", required=True, help="best_model.pth of train() (a pickled module) or a state-dict file")
     ap.add_argument("--images", required=True, help="directory of 2-D .npy images (float32 or uint8)")
@@ -320,7 +341,20 @@ def main(argv=None):
     ap.add_argument("--keep-largest", type=int, default=None, help="keep only this many (1..8) largest components of each class")
     ap.add_argument("--fill-holes", action="store_true", help="fill the holes of each class")
     ap.add_argument("--connectivity", type=int, default=8, choices=[4, 8], help="connectivity of the components")
-    args = ap.parse_args(argv)
+    ap.add_argument("--crop", type=int, default=None, metavar="SIZE", help="centre-crop every raw image to SIZE x SIZE first (the reference: 475)")
+    ap.add_argument("--unsharp", type=float, nargs=2, default=None, metavar=("RADIUS", "AMOUNT"),
+                    help=f"unsharp mask (skimage.filters.unsharp_mask) with this Gaussian radius (<= {_preprocess.PRE_MAX_RADIUS}) and amount")
+    ap.add_argument("--preserve-range", action="store_true", help="with --unsharp: keep a uint8 image's 0..255 range and do not clip")
+    ap.add_argument("--normalize", default="none", choices=sorted(_preprocess.NORMALIZERS),
+                    help="per-image normalisation after crop and unsharp: (x - mean) / std, (x - min) / (max - min), or rows over their L2 norm")
+    return ap
+
+
+def main(argv=None):
+    args = build_parser().parse_args(argv)
+    if args.preserve_range and args.unsharp is None:
+        raise SystemExit("--preserve-range needs --unsharp")
+    pre = _preprocess.from_options(args.crop, args.unsharp, args.preserve_range, args.normalize)      # (None: the calls of before)
     if not torch.cuda.is_available():
         raise RuntimeError("cmunet_amd.infer needs a ROCm GPU; there is no CPU fallback in this package")
     model = load_segmentation_model(args.model, dtype=args.dtype)
@@ -328,7 +362,8 @@ def main(argv=None):
     size = (None if args.tile else 256) if args.size is None else (args.size or None)
     written = segment_files(model, paths, args.out, size=size, batch=args.batch, threshold=args.threshold, tile=args.tile,
                             stride=args.stride, window=args.window, pad=args.pad, tta=None if args.tta == "none" else args.tta,
-                            min_size=args.min_size, keep_largest=args.keep_largest, fill_holes=args.fill_holes, connectivity=args.connectivity)
+                            min_size=args.min_size, keep_largest=args.keep_largest, fill_holes=args.fill_holes, connectivity=args.connectivity,
+                            preprocess=pre)
     print(f"{len(written)} masks written to {args.out}")
     return 0
 

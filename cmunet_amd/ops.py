@@ -1350,3 +1350,99 @@ def filter_components(src, cls, labels=None, sizes=None, min_size=0, keep_roots=
          int(removed_value), _p(hole_labels), _p(hole_touches), _p(class_values), 0 if class_values is None else class_values.numel(),
          _p(out), B, H, W, _stream())
     return out
+
+
+# ---- image preprocessing (csrc/preprocess.hip) ------------------------------------------------
+PRE_MAX_RADIUS = 16      # CMU_PRE_MAX_RADIUS: the largest Gaussian radius of the unsharp mask (half-width 64)
+
+
+def _pre_check(what, t):
+    if not t.is_cuda:
+        raise RuntimeError(f"{what} runs on the GPU only; there is no CPU fallback in this package")
+    if t.dtype not in (torch.uint8, torch.float32) or t.dim() != 3 or not t.is_contiguous():
+        raise ValueError(f"{what}: a contiguous (B,H,W) uint8 or float32 tensor, got {tuple(t.shape)} {t.dtype}")
+    B, H, W = t.shape
+    if B < 1 or H < 1 or W < 1 or H * W >= 2 ** 31 or B > 65535:
+        raise ValueError(f"{what}: 1 <= B <= 65535, 1 <= H, W and H * W < 2**31, got {tuple(t.shape)}")
+    return B, H, W, int(t.dtype == torch.uint8)
+
+
+def _pre_stats_arg(what, stats, B, device):
+    if stats.dtype != torch.float64 or tuple(stats.shape) != (B, 4) or not stats.is_contiguous() or stats.device != device:
+        raise ValueError(f"{what}: stats must be a contiguous (B,4) float64 tensor on the image's device, got {tuple(stats.shape)} {stats.dtype}")
+    return stats
+
+
+def pre_stats(x):
+    """x (B,H,W) uint8 / float32 -> (B,4) float64: mean, population standard deviation, min, max of every image."""
+    B, H, W, u8 = _pre_check("pre_stats", x)
+    stats = torch.empty(B, 4, dtype=torch.float64, device=x.device)
+    call("cmu_pre_stats", _p(x), u8, _p(stats), B, H, W, _stream())
+    return stats
+
+
+def pre_standardize(x, stats):
+    """float32((float64(x) - stats[b,0]) / stats[b,1])."""
+    B, H, W, u8 = _pre_check("pre_standardize", x)
+    out = torch.empty(B, H, W, dtype=torch.float32, device=x.device)
+    call("cmu_pre_standardize", _p(x), u8, _p(_pre_stats_arg("pre_standardize", stats, B, x.device)), _p(out), B, H, W, _stream())
+    return out
+
+
+def pre_minmax(x, stats):
+    """(x - stats[b,2]) / float32(stats[b,3] - stats[b,2]) in the reference's arithmetic (one float32 division)."""
+    B, H, W, u8 = _pre_check("pre_minmax", x)
+    out = torch.empty(B, H, W, dtype=torch.float32, device=x.device)
+    call("cmu_pre_minmax", _p(x), u8, _p(_pre_stats_arg("pre_minmax", stats, B, x.device)), _p(out), B, H, W, _stream())
+    return out
+
+
+def pre_row_normalize(x):
+    """Every row over its Euclidean norm (float64), a zero row unchanged; float32."""
+    B, H, W, u8 = _pre_check("pre_row_normalize", x)
+    out = torch.empty(B, H, W, dtype=torch.float32, device=x.device)
+    call("cmu_pre_row_normalize", _p(x), u8, _p(out), B, H, W, _stream())
+    return out
+
+
+def pre_unsharp(x, weights, amount, scale_div=1.0, clip=False, stats=None, tmp=None):
+    """The two passes of the unsharp mask: ``weights`` (lw + 1,) float32 on the device (tap at distance k), f = x / scale_div,
+    out = f + (f - blur(f)) * amount, with ``clip`` clipped to [0,1] ([-1,1] where stats[b,2] < 0).  ``tmp``: the (B,H,W) float32
+    plane between the passes (allocated when None)."""
+    B, H, W, u8 = _pre_check("pre_unsharp", x)
+    lw = int(weights.numel()) - 1
+    if weights.dtype != torch.float32 or weights.dim() != 1 or not weights.is_contiguous() or not 0 <= lw <= 4 * PRE_MAX_RADIUS:
+        raise ValueError(f"pre_unsharp: weights must be 1..{4 * PRE_MAX_RADIUS + 1} contiguous float32 taps")
+    if tmp is None:
+        tmp = torch.empty(B, H, W, dtype=torch.float32, device=x.device)
+    elif tmp.dtype != torch.float32 or tuple(tmp.shape) != (B, H, W) or not tmp.is_contiguous():
+        raise ValueError("pre_unsharp: tmp must be a contiguous float32 tensor of the image's shape")
+    if stats is not None:
+        _pre_stats_arg("pre_unsharp", stats, B, x.device)
+    out = torch.empty(B, H, W, dtype=torch.float32, device=x.device)
+    call("cmu_pre_blur_rows", _p(x), u8, float(scale_div), _p(weights), lw, _p(tmp), B, H, W, _stream())
+    call("cmu_pre_unsharp_cols", _p(x), u8, float(scale_div), _p(tmp), _p(weights), lw, float(amount), int(bool(clip)), _p(stats), _p(out),
+         B, H, W, _stream())
+    return out
+
+
+def pre_crop(x, y0, x0, OH, OW):
+    """x[:, y0:y0+OH, x0:x0+OW] as a new contiguous tensor (uint8 or float32)."""
+    B, H, W, u8 = _pre_check("pre_crop", x)
+    if not (OH >= 1 and OW >= 1 and 0 <= y0 and 0 <= x0 and y0 + OH <= H and x0 + OW <= W):
+        raise ValueError(f"pre_crop: the window ({y0}, {x0}) + ({OH}, {OW}) leaves the {H} x {W} image")
+    out = torch.empty(B, OH, OW, dtype=x.dtype, device=x.device)
+    call("cmu_pre_crop", _p(x), 1 if u8 else 4, _p(out), B, H, W, int(y0), int(x0), int(OH), int(OW), _stream())
+    return out
+
+
+def pre_integrate_masks(masks):
+    """masks (B,M,H,W) uint8 -> (B,H,W) uint8: 1 where any of the M masks is non-zero."""
+    if not masks.is_cuda:
+        raise RuntimeError("pre_integrate_masks runs on the GPU only; there is no CPU fallback in this package")
+    if masks.dtype != torch.uint8 or masks.dim() != 4 or not masks.is_contiguous() or min(masks.shape) < 1 or masks.shape[0] > 65535:
+        raise ValueError(f"pre_integrate_masks: a contiguous (B,M,H,W) uint8 tensor, got {tuple(masks.shape)} {masks.dtype}")
+    B, M, H, W = masks.shape
+    out = torch.empty(B, H, W, dtype=torch.uint8, device=masks.device)
+    call("cmu_pre_integrate_masks", _p(masks), _p(out), B, M, H * W, _stream())
+    return out

@@ -935,6 +935,34 @@ int cmu_filter_components(const uint8_t* src, int cls, const int32_t* labels, co
                           int n_keep, int removed_value, const int32_t* hole_labels, const uint8_t* hole_touches,
                           const uint8_t* class_values, int n_values, uint8_t* out, int B, int H, int W, void* stream);
 
+/* ---- image preprocessing (csrc/preprocess.hip): the reference's data_processing/pre_processing.py -------------
+ * Planes are contiguous (B,H,W), 1 <= B <= 65535, H, W >= 1, H * W < 2^31; x is uint8 (is_u8 = 1) or float32 (is_u8 = 0).  Every kernel is
+ * deterministic (fixed summation order, no float atomics).  `stats` is (B,4) float64 per image: mean, population standard deviation
+ * (numpy's np.std: sqrt(sum((x - mean)^2) / N)), min, max.
+ * cmu_pre_stats: one workgroup per image, sums in float64; a uint8 image's sum is an exact integer, so its mean is one division.          */
+int cmu_pre_stats(const void* x, int is_u8, double* stats, int B, int H, int W, void* stream);
+/* out = float32((double(x) - stats[b][0]) / stats[b][1]); a zero deviation gives nan / inf as the division does.                         */
+int cmu_pre_standardize(const void* x, int is_u8, const double* stats, float* out, int B, int H, int W, void* stream);
+/* out = (x - lo) / float32(hi - lo) with lo = stats[b][2], hi = stats[b][3]: uint8 differences are exact integers, float32 ones a single
+ * float32 subtraction; the quotient is one correctly rounded float32 division (hi == lo: nan where x == lo).                             */
+int cmu_pre_minmax(const void* x, int is_u8, const double* stats, float* out, int B, int H, int W, void* stream);
+/* every row divided by its Euclidean norm (float64 norm and quotient, then one cast); a zero row stays zero.                            */
+int cmu_pre_row_normalize(const void* x, int is_u8, float* out, int B, int H, int W, void* stream);
+/* The largest Gaussian radius (sigma) of the unsharp mask; the half-width of its kernel is lw = int(4 * radius + 0.5) <= 64.            */
+#define CMU_PRE_MAX_RADIUS 16
+#define CMU_PRE_MAX_LW 64
+/* Unsharp mask in two passes.  f = float32(x) / scale_div (255 for skimage's uint8 -> [0,1] conversion, else 1).  weights: lw + 1 float32
+ * on the device, w[k] the normalised Gaussian tap at distance k.  Borders are scipy's 'reflect' (d c b a | a b c d), repeated as needed.
+ * cmu_pre_blur_rows: tmp = f blurred along W.  cmu_pre_unsharp_cols: blurred = tmp blurred along H, out = f + (f - blurred) * amount,
+ * then with clip != 0 clipped to [0,1] -- or to [-1,1] for an image whose stats[b][2] (min) is negative (stats may be NULL: [0,1]).       */
+int cmu_pre_blur_rows(const void* x, int is_u8, float scale_div, const float* weights, int lw, float* tmp, int B, int H, int W, void* stream);
+int cmu_pre_unsharp_cols(const void* x, int is_u8, float scale_div, const float* tmp, const float* weights, int lw, float amount, int clip,
+                         const double* stats, float* out, int B, int H, int W, void* stream);
+/* dst (B,OH,OW) = src[:, y0:y0+OH, x0:x0+OW] for elements of elem_bytes = 1 or 4.                                                        */
+int cmu_pre_crop(const void* src, int elem_bytes, void* dst, int B, int H, int W, int y0, int x0, int OH, int OW, void* stream);
+/* out (B,HW) uint8 = 1 where any of the M masks (B,M,HW) uint8 is non-zero at the pixel, else 0.                                         */
+int cmu_pre_integrate_masks(const uint8_t* masks, uint8_t* out, int B, int M, int64_t HW, void* stream);
+
 /* Measurement support (bench.py's roofline block; no reference counterpart): the 16-bit MFMA rate this chip SUSTAINS.
  * Every wave of a one-workgroup-per-CU grid issues iters x 8 back-to-back 32x32x16 MFMAs from registers (no LDS, no
  * memory) or -- lds_fed = 1 -- the same MFMAs fed from LDS at the persistent conv kernel's ratio (6 fragment reads of 1 KB
