@@ -216,6 +216,11 @@ _SIGS = {
     "cmu_select_largest": (_I, [_P, _I, _P, _I, _I, _I, _P]),
     "cmu_border_components": (_I, [_P, _P, _I, _I, _I, _P]),
     "cmu_filter_components": (_I, [_P, _I, _P, _P, _I, _P, _I, _I, _P, _P, _P, _I, _P, _I, _I, _I, _P]),
+    "cmu_edt_columns": (_I, [_P, _I, _I, _P, _I, _I, _I, _P]),
+    "cmu_edt_rows": (_I, [_P, _P, _P, _P, _P, _I, _I, _I, _I, _I, _I, _I, _P]),
+    "cmu_surface_border": (_I, [_P, _I, _P, _I, _I, _I, _P]),
+    "cmu_surface_reduce": (_I, [_P, _I, _P, _I, _P, _P, _P, _I, _I, _I, _P]),
+    "cmu_surface_select": (_I, [_P, _P, _P, _I, _P, _P, _I, _I, _I, _P]),
     "cmu_pre_stats": (_I, [_P, _I, _P, _I, _I, _I, _P]),
     "cmu_pre_standardize": (_I, [_P, _I, _P, _P, _I, _I, _I, _P]),
     "cmu_pre_minmax": (_I, [_P, _I, _P, _P, _I, _I, _I, _P]),

@@ -5,7 +5,7 @@
   segment_files(model, paths, out_dir)                    ``.npy`` images -> ``<stem>_mask.npy``
   python -m cmunet_amd.infer --model M --images DIR --out DIR [--size 256] [--batch 32] [--dtype f16] [--threshold 0.5]
                               [--tile 256 [--stride 128] [--window gaussian] [--pad reflect]] [--tta d4]
-                              [--min-size 50] [--keep-largest 2] [--fill-holes] [--connectivity 8]
+                              [--min-size 50] [--keep-largest 2] [--fill-holes] [--connectivity 8] [--opening R] [--closing R]
                               [--crop 475] [--unsharp RADIUS AMOUNT [--preserve-range]] [--normalize {none,intensity,minmax,rows}]
 
 Per chunk of same-sized images: the training pipeline's resize (``ops.resize_bicubic``: Pillow's bicubic in the image's own
@@ -23,6 +23,7 @@ device chunk of raw images passes through it first, so raw image -> mask is one 
 the PREPROCESSED size (the cropped one).
 """
 import argparse
+import math
 import os
 
 import numpy as np
@@ -135,6 +136,9 @@ class Segmenter:
     counts source pixels), on the plain and the tiled path, for every class but 0: components (``connectivity`` 4 or 8) of fewer
     than ``min_size`` pixels are removed, then only the ``keep_largest`` (1..8) largest stay, then holes are filled.  The network and
     blend passes then write class indices and the clean-up's last pass applies ``class_values``.  ``prob`` outputs are untouched.
+    ``opening`` / ``closing`` (None, or the radius >= 0 of a Euclidean disk) belong to the same clean-up and switch it on as well: every
+    class is opened, then closed (csrc/edt.hip: an exact distance transform, the cost does not grow with the radius), before the three
+    steps above, so a vessel broken by a gap of a pixel or two is one component when ``keep_largest`` looks at it.
 
     ``preprocess`` (None: the calls above run exactly as before): a callable ``(n,H,W) uint8 / float32 device batch -> (n,H',W')`` --
     ``preprocess.Preprocess`` -- applied to every chunk before the resize / tiling.  Masks (and ``min_size``) are then at the
@@ -142,7 +146,7 @@ class Segmenter:
     H' x W'."""
 
     def __init__(self, model, size=256, batch=32, threshold=0.5, class_values=None, tile=None, stride=None, window="gaussian",
-                 pad="reflect", tta=None, min_size=None, keep_largest=None, fill_holes=False, connectivity=8, preprocess=None):
+                 pad="reflect", tta=None, min_size=None, keep_largest=None, fill_holes=False, connectivity=8, preprocess=None, opening=None, closing=None):
         self.model, self.size, self.batch, self.threshold = model, size, int(batch), threshold
         self.mult = 1 << (_depth(model) - 1)
         if size is not None and (int(size) <= 0 or int(size) % self.mult):
@@ -190,7 +194,13 @@ class Segmenter:
         self.min_size = None if min_size is None else int(min_size)
         self.keep_largest = None if keep_largest is None else int(keep_largest)
         self.fill_holes, self.connectivity = fill_holes, connectivity
-        self.post = self.min_size is not None or self.keep_largest is not None or self.fill_holes
+        for name, r in (("opening", opening), ("closing", closing)):
+            if r is not None and (isinstance(r, bool) or not isinstance(r, (int, float)) or not math.isfinite(r) or r < 0):
+                raise ValueError(f"Segmenter: {name} must be None or a real radius >= 0, got {r!r}")
+        self.opening = None if opening is None else float(opening)
+        self.closing = None if closing is None else float(closing)
+        self.post = (self.min_size is not None or self.keep_largest is not None or self.fill_holes or self.opening is not None
+                     or self.closing is not None)
         if preprocess is not None and not callable(preprocess):
             raise ValueError(f"Segmenter: preprocess must be None or a callable, got {type(preprocess).__name__}")
         self.preprocess = preprocess
@@ -256,7 +266,7 @@ class Segmenter:
         if self.post:      # on the mask at the image's own size: min_size counts source pixels
             K = max(int(self.model.conv_last.weight.shape[0]), 2)
             lab = postprocess.clean_mask(lab, range(1, K), self.min_size or 0, self.keep_largest, self.fill_holes, self.connectivity,
-                                         self._table(src.device, head=False))
+                                         self._table(src.device, head=False), opening=self.opening or 0, closing=self.closing or 0)
         return lab if prob_class is None else (lab, prob)
 
     def segment(self, images, prob_class=None):
@@ -341,6 +351,8 @@ def build_parser():
     ap.add_argument("--keep-largest", type=int, default=None, help="keep only this many (1..8) largest components of each class")
     ap.add_argument("--fill-holes", action="store_true", help="fill the holes of each class")
     ap.add_argument("--connectivity", type=int, default=8, choices=[4, 8], help="connectivity of the components")
+    ap.add_argument("--opening", type=float, default=None, metavar="R", help="open each class with a Euclidean disk of this radius first")
+    ap.add_argument("--closing", type=float, default=None, metavar="R", help="then close each class with a disk of this radius (joins gaps)")
     ap.add_argument("--crop", type=int, default=None, metavar="SIZE", help="centre-crop every raw image to SIZE x SIZE first (the reference: 475)")
     ap.add_argument("--unsharp", type=float, nargs=2, default=None, metavar=("RADIUS", "AMOUNT"),
                     help=f"unsharp mask (skimage.filters.unsharp_mask) with this Gaussian radius (<= {_preprocess.PRE_MAX_RADIUS}) and amount")
@@ -363,7 +375,7 @@ def main(argv=None):
     written = segment_files(model, paths, args.out, size=size, batch=args.batch, threshold=args.threshold, tile=args.tile,
                             stride=args.stride, window=args.window, pad=args.pad, tta=None if args.tta == "none" else args.tta,
                             min_size=args.min_size, keep_largest=args.keep_largest, fill_holes=args.fill_holes, connectivity=args.connectivity,
-                            preprocess=pre)
+                            preprocess=pre, opening=args.opening, closing=args.closing)
     print(f"{len(written)} masks written to {args.out}")
     return 0
 

@@ -31,6 +31,8 @@ of int64 / int32 / uint8 / fp32 / fp64, read in their own dtype: 1-8 bytes per p
 ``NLLLoss(activation, ignore_channels, threshold)`` one-hot targets whose arg-max over the kept channels is taken in the kernel; both run
 on ``cmu_index_ce_fwd`` / ``_bwd`` (2..8 classes), which yield three fp64 sums from which torch's reductions follow on the device.
 """
+import collections
+import math
 import weakref
 
 import torch
@@ -710,6 +712,136 @@ class components(Metric):
     def forward(self, y_pr, y_gt):
         c = self.per_image(y_pr, y_gt).double()
         return (c[:, 0] - c[:, 1]).abs().mean()
+
+
+# ---------------------------------------------------------------------------------------------------
+# surface-distance scores on the exact distance transform (csrc/edt.hip; no reference counterpart)
+# ---------------------------------------------------------------------------------------------------
+SurfaceDistances = collections.namedtuple(
+    "SurfaceDistances", "hd hd_percentile assd nsd mean_pr_to_gt mean_gt_to_pr n_pr n_gt")
+
+
+def _check_surface_cfg(what, tolerance, percentile):
+    if isinstance(tolerance, bool) or not isinstance(tolerance, (int, float)) or not math.isfinite(tolerance) or tolerance < 0:
+        raise ValueError(f"{what}: tolerance must be a real number >= 0, got {tolerance!r}")
+    if isinstance(percentile, bool) or not isinstance(percentile, (int, float)) or not 0 <= percentile <= 100:
+        raise ValueError(f"{what}: percentile must lie in 0..100, got {percentile!r}")
+
+
+def _surface_of_masks(a, b, tolerance, percentile):
+    """a, b (B,H,W) uint8 -> SurfaceDistances of (B,) tensors.  Launches only: no host read."""
+    tol2 = min(int(math.floor(float(tolerance) * float(tolerance))), 2 ** 31 - 1)
+    g = torch.empty(a.shape, dtype=torch.int32, device=a.device)
+    to_b = ops.edt_rows(ops.edt_columns(b, -1, True, g), "dist2")          # every pixel's squared distance to b's border
+    sa, ca, ma = ops.surface_reduce(a, to_b, tol2)                         # ... gathered on a's border
+    to_a = ops.edt_rows(ops.edt_columns(a, -1, True, g), "dist2", out=to_b)
+    sb, cb, mb = ops.surface_reduce(b, to_a, tol2)
+    n_a, n_b = ca[:, 0], cb[:, 0]
+    na, nb = n_a.double(), n_b.double()
+    n = na + nb
+    both_empty, one_empty = n == 0, (n_a == 0) != (n_b == 0)
+    zero, one, inf = torch.zeros_like(n), torch.ones_like(n), torch.full_like(n, float("inf"))
+
+    def dist(x):      # a distance: 0 when both borders are empty, inf when exactly one is
+        return torch.where(both_empty, zero, torch.where(one_empty, inf, x))
+
+    mean_ab, mean_ba = sa[:, 0] / na, sb[:, 0] / nb
+    hd = torch.maximum(sa[:, 1], sb[:, 1])
+    # np.percentile(hstack(d_ab, d_ba), q), numpy's default 'linear' method: virtual index (n - 1) * q / 100 between two exact order statistics
+    vi = (n - 1.0) * (float(percentile) / 100.0)
+    lo = vi.floor()
+    k0 = torch.minimum(lo.clamp_min(0.0), (n - 1.0).clamp_min(0.0))
+    k1 = torch.minimum(k0 + 1.0, (n - 1.0).clamp_min(0.0))
+    ranks = torch.where(both_empty.unsqueeze(1), torch.full_like(k0, -1.0).unsqueeze(1), torch.stack((k0, k1), 1)).to(torch.int32).contiguous()
+    roots = ops.surface_select(ma, mb, ranks)[1]
+    lo_v, hi_v, t = roots[:, 0], roots[:, 1], vi - lo
+    diff = hi_v - lo_v
+    pct = torch.where(t >= 0.5, hi_v - diff * (1.0 - t), lo_v + diff * t)
+    nsd = torch.where(both_empty, one, (ca[:, 2] + cb[:, 2]).double() / n)      # (one border empty: nothing lies within: 0 / n)
+    return SurfaceDistances(dist(hd), dist(pct), dist((mean_ab + mean_ba) / 2.0), nsd, dist(mean_ab), dist(mean_ba), n_a, n_b)
+
+
+def surface_distances(pr_mask, gt_mask, tolerance=1.0, percentile=95.0):
+    """Surface-distance scores of two device masks ((H,W) or (B,H,W), foreground = ``> 0``), per image, as fp64 tensors (0-dim for (H,W)
+    inputs) in a ``SurfaceDistances`` tuple.  A mask's border is ``mask & ~binary_erosion(mask, cross, border_value=0)``: its pixels
+    with a 4-neighbour that is background or outside the image (the rule of medpy and MONAI).  With d(A->B) the Euclidean distances
+    from A's border pixels to the nearest border pixel of B:
+
+      hd             max over both directions
+      hd_percentile  ``np.percentile(hstack(d(A->B), d(B->A)), percentile)`` with numpy's default linear interpolation -- medpy's
+                     ``hd95``: the percentile of the POOLED distances, NOT the max of the two directions' percentiles
+      assd           (mean d(A->B) + mean d(B->A)) / 2; the two means are ``mean_pr_to_gt`` and ``mean_gt_to_pr``
+      nsd            surface Dice at ``tolerance``: (#{d(A->B) <= tol} + #{d(B->A) <= tol}) / (n_A + n_B), compared exactly as
+                     squared distance <= floor(tol^2)
+      n_pr, n_gt     the border pixel counts (int32)
+
+    Both borders empty: distances 0, nsd 1.  Exactly one empty: distances inf, nsd 0 (as ``hausdorff_distance_mask``).  Squared
+    distances, counts and the two order statistics are exact integers; sums are fp64 in a fixed order.  1 <= H, W <= 4096."""
+    _check_surface_cfg("surface_distances", tolerance, percentile)
+    if not (torch.is_tensor(pr_mask) and torch.is_tensor(gt_mask) and pr_mask.is_cuda and gt_mask.is_cuda):
+        raise RuntimeError("surface_distances runs on the GPU only; there is no CPU fallback in this package")
+    a, batched = _as_masks(pr_mask)
+    b, _ = _as_masks(gt_mask)
+    if a.shape != b.shape:
+        raise ValueError("both masks must have the same shape")
+    ops._edt_check("surface_distances", a, torch.uint8)
+    out = _surface_of_masks(a, b, tolerance, percentile)
+    return out if batched else SurfaceDistances(*(v[0] for v in out))
+
+
+def _surface_pair(y_pr, y_gt, threshold, what):
+    """Two-class logits and a one-hot target, binarised as ``hausdorff`` does: softmax > threshold on channel 1, the target's channel 1."""
+    _check_two_class(y_pr, y_gt, what)
+    B, _, H, W = y_pr.shape
+    yp = torch.empty(B, H, W, dtype=torch.float32, device=y_pr.device)
+    ops.softmax2_threshold(y_pr.detach().float().contiguous(), threshold, yp)
+    return _as_masks(yp)[0], _as_masks(y_gt.detach()[:, 1])[0]
+
+
+class _SurfaceMetric(Metric):
+    def __init__(self, threshold=0.5, tolerance=1.0, percentile=95.0, **kwargs):
+        super().__init__(**kwargs)
+        if not 0.0 < float(threshold) < 1.0:
+            raise ValueError(f"{self.__name__}: threshold must lie inside (0, 1), got {threshold!r}")
+        _check_surface_cfg(self.__name__, tolerance, percentile)
+        self.threshold, self.tolerance, self.percentile = float(threshold), tolerance, percentile
+
+    def per_image(self, y_pr, y_gt):
+        """SurfaceDistances of (B,) tensors."""
+        a, b = _surface_pair(y_pr, y_gt, self.threshold, self.__name__)
+        ops._edt_check(self.__name__, a, torch.uint8)
+        return _surface_of_masks(a, b, self.tolerance, self.percentile)
+
+
+class HausdorffDistance95(_SurfaceMetric):
+    """The ``percentile``-th (default 95) percentile Hausdorff distance of ``surface_distances`` (medpy's ``hd95``: pooled over both
+    directions), fp64 mean over the batch (inf if any image is inf).  Two-class (B,2,H,W) logits and one-hot targets, as ``hausdorff``."""
+    __name__ = "hd95"
+
+    def __init__(self, percentile=95.0, **kwargs):
+        super().__init__(percentile=percentile, **kwargs)
+
+    def forward(self, y_pr, y_gt):
+        return self.per_image(y_pr, y_gt).hd_percentile.mean()
+
+
+class AverageSurfaceDistance(_SurfaceMetric):
+    """The average symmetric surface distance of ``surface_distances``, fp64 mean over the batch."""
+    __name__ = "assd"
+
+    def forward(self, y_pr, y_gt):
+        return self.per_image(y_pr, y_gt).assd.mean()
+
+
+class SurfaceDice(_SurfaceMetric):
+    """The surface Dice (normalised surface distance) at ``tolerance`` pixels of ``surface_distances``, fp64 mean over the batch."""
+    __name__ = "surface_dice"
+
+    def __init__(self, tolerance=1.0, **kwargs):
+        super().__init__(tolerance=tolerance, **kwargs)
+
+    def forward(self, y_pr, y_gt):
+        return self.per_image(y_pr, y_gt).nsd.mean()
 
 
 # ---------------------------------------------------------------------------------------------------

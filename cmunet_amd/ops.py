@@ -1352,6 +1352,98 @@ def filter_components(src, cls, labels=None, sizes=None, min_size=0, keep_roots=
     return out
 
 
+# ---- exact Euclidean distance transform, disk morphology, surface distances (csrc/edt.hip) -----
+EDT_MAX_SIDE = 4096      # CMU_EDT_MAX_SIDE: 2 * 4095**2 < 2**31
+
+
+def _edt_check(what, t, dtype, cls=-1):
+    B, H, W = _cc_check(what, t, dtype)
+    if H > EDT_MAX_SIDE or W > EDT_MAX_SIDE:
+        raise ValueError(f"{what}: H, W <= {EDT_MAX_SIDE}, got {tuple(t.shape)}")
+    if isinstance(cls, bool) or int(cls) != cls or not -257 <= int(cls) <= 255:
+        raise ValueError(f"{what}: cls in 0..255, -1 or -2 - c, got {cls!r}")
+    return B, H, W
+
+
+def _edt_scratch(what, name, t, like, dtype):
+    """A caller's scratch / output tensor, or a fresh one: contiguous, ``like``'s shape and device."""
+    if t is None:
+        return torch.empty(like.shape, dtype=dtype, device=like.device)
+    if t.dtype != dtype or t.shape != like.shape or not t.is_contiguous() or t.device != like.device:
+        raise ValueError(f"{what}: {name} must be a contiguous {dtype} tensor of shape {tuple(like.shape)} on the map's device")
+    return t
+
+
+def edt_columns(src, cls=-1, border=False, g=None):
+    """src (B,H,W) uint8 -> g (B,H,W) int32: the vertical distance to the nearest site of the pixel's column, 16384 where the column
+    has none.  Sites: the rule ``cls`` (the codes of ``label_components``), or with ``border`` the rule's border pixels."""
+    B, H, W = _edt_check("edt_columns", src, torch.uint8, cls)
+    g = _edt_scratch("edt_columns", "g", g, src, torch.int32)
+    call("cmu_edt_columns", _p(src), int(cls), int(bool(border)), _p(g), B, H, W, _stream())
+    return g
+
+
+def edt_rows(g, want="dist2", base=None, greater=False, t=0, v_hit=-1, v_miss=-1, out=None):
+    """The row pass over ``g`` of ``edt_columns``.  ``want``: 'dist2' -> int32 squared distances (-1: the image has no site); 'dist' ->
+    float32 roots (inf); 'map' -> uint8: a site keeps ``base``; another pixel with dist2 <= t (``greater``: dist2 > t, -1 infinitely
+    far) receives ``v_hit``, else ``v_miss``; -1 keeps ``base``."""
+    B, H, W = _edt_check("edt_rows", g, torch.int32)
+    if want not in ("dist2", "dist", "map"):
+        raise ValueError(f"edt_rows: want must be 'dist2', 'dist' or 'map', got {want!r}")
+    if want != "map":
+        out = _edt_scratch("edt_rows", "out", out, g, torch.int32 if want == "dist2" else torch.float32)
+        call("cmu_edt_rows", _p(g), _p(out if want == "dist2" else None), _p(out if want == "dist" else None), None, None, 0, 0, -1, -1,
+             B, H, W, _stream())
+        return out
+    if base is None or base.dtype != torch.uint8 or base.shape != g.shape or not base.is_contiguous() or base.device != g.device:
+        raise ValueError(f"edt_rows: base must be a contiguous uint8 tensor of shape {tuple(g.shape)} on g's device")
+    if not (0 <= int(t) < 2 ** 31 and -1 <= int(v_hit) <= 255 and -1 <= int(v_miss) <= 255):
+        raise ValueError(f"edt_rows: 0 <= t < 2**31 and v_hit, v_miss in -1..255, got {t}, {v_hit}, {v_miss}")
+    out = _edt_scratch("edt_rows", "out", out, g, torch.uint8)
+    call("cmu_edt_rows", _p(g), None, None, _p(base), _p(out), int(bool(greater)), int(t), int(v_hit), int(v_miss), B, H, W, _stream())
+    return out
+
+
+def surface_border(src, cls=-1):
+    """src (B,H,W) uint8 -> (B,H,W) uint8: 1 on the pixels of the rule's set that have a 4-neighbour outside the set or the image."""
+    B, H, W = _edt_check("surface_border", src, torch.uint8, cls)
+    out = torch.empty_like(src)
+    call("cmu_surface_border", _p(src), int(cls), _p(out), B, H, W, _stream())
+    return out
+
+
+def surface_reduce(src, dist2, tol2=0, cls=-1, masked=None, want_masked=True):
+    """Over the border pixels of ``src``'s set, ``dist2`` being the transform to another border -> (sums (B,2) float64 = (sum of the
+    roots, root of the largest), counts (B,3) int32 = (n, max dist2, number <= tol2), masked (B,H,W) int32 = dist2 on the border pixels and -2 elsewhere, or None)."""
+    B, H, W = _edt_check("surface_reduce", src, torch.uint8, cls)
+    if dist2.dtype != torch.int32 or dist2.shape != src.shape or not dist2.is_contiguous() or dist2.device != src.device:
+        raise ValueError(f"surface_reduce: dist2 must be a contiguous int32 tensor of shape {tuple(src.shape)} on the map's device")
+    if not 0 <= int(tol2) < 2 ** 31:
+        raise ValueError(f"surface_reduce: 0 <= tol2 < 2**31, got {tol2}")
+    if want_masked or masked is not None:
+        masked = _edt_scratch("surface_reduce", "masked", masked, src, torch.int32)
+    sums = torch.empty(B, 2, dtype=torch.float64, device=src.device)
+    counts = torch.empty(B, 3, dtype=torch.int32, device=src.device)
+    call("cmu_surface_reduce", _p(src), int(cls), _p(dist2), int(tol2), _p(masked), _p(sums), _p(counts), B, H, W, _stream())
+    return sums, counts, masked
+
+
+def surface_select(masked_a, masked_b, ranks):
+    """The ``ranks[b, r]``-th smallest (from 0) non-negative entry of image b of both masked maps together -> (values (B,R) int32, -1 if
+    there are not that many; roots (B,R) float64, inf there).  ``ranks``: (B,R) int32 on the device, R = 1 or 2."""
+    B, H, W = _edt_check("surface_select", masked_a, torch.int32)
+    if masked_b.dtype != torch.int32 or masked_b.shape != masked_a.shape or not masked_b.is_contiguous() or masked_b.device != masked_a.device:
+        raise ValueError("surface_select: both masked maps must be contiguous int32 tensors of one shape on one device")
+    if ranks.dtype != torch.int32 or ranks.dim() != 2 or ranks.shape[0] != B or ranks.shape[1] not in (1, 2) or not ranks.is_contiguous() \
+            or ranks.device != masked_a.device:
+        raise ValueError(f"surface_select: ranks must be a contiguous (B,1) or (B,2) int32 tensor on the maps' device, got {tuple(ranks.shape)} {ranks.dtype}")
+    R = int(ranks.shape[1])
+    vals = torch.empty(B, R, dtype=torch.int32, device=masked_a.device)
+    roots = torch.empty(B, R, dtype=torch.float64, device=masked_a.device)
+    call("cmu_surface_select", _p(masked_a), _p(masked_b), _p(ranks), R, _p(vals), _p(roots), B, H, W, _stream())
+    return vals, roots
+
+
 # ---- image preprocessing (csrc/preprocess.hip, DESIGN.md section 4.22) ------------------------------------------------
 PRE_MAX_RADIUS = 16      # CMU_PRE_MAX_RADIUS: the largest Gaussian radius of the unsharp mask (half-width 64)
 

@@ -935,6 +935,43 @@ int cmu_filter_components(const uint8_t* src, int cls, const int32_t* labels, co
                           int n_keep, int removed_value, const int32_t* hole_labels, const uint8_t* hole_touches,
                           const uint8_t* class_values, int n_values, uint8_t* out, int B, int H, int W, void* stream);
 
+/* ---------------------------------------------------------------------------------------------
+ * Exact Euclidean distance transform of uint8 maps, disk morphology and surface distances (csrc/edt.hip, csrc/edt_scan.h, DESIGN.md
+ * section 4.23; no reference counterpart: users of the reference call scipy.ndimage on the host).  Shapes: 1 <= B <= 65535,
+ * 1 <= H, W <= 4096 (2 * 4095^2 < 2^31); anything else is CMU_ERR_ARG.  Images of a batch are independent.  Every result but the fp64
+ * sum is an integer; no atomics; the same bits on every call.  There is no workspace query: scratch is the explicit tensors named
+ * below, every element of every output is written on every call and nothing is read before it is written.
+ * Site rule: the codes of cmu_label_components (cls in 0..255: src == cls; -1: src != 0; -2 - c: src != c).
+ *
+ * The transform is two launches.  cmu_edt_columns: g (B,H,W) int32 = vertical distance to the nearest site of the pixel's own
+ * column, 16384 where the column holds none.  border != 0: the sites are the rule's BORDER pixels instead: pixels of the rule's set with
+ * a 4-neighbour outside the set or outside the image (mask & ~binary_erosion(mask, cross, border_value=0)).
+ * cmu_edt_rows: from g, any of (NULL = not wanted, at least one)
+ *   dist2 (B,H,W) int32    the squared Euclidean distance to the nearest site of the pixel's image; 0 on a site; -1 at EVERY pixel of an
+ *                          image that holds no site at all (this library's rule: scipy's answer there is meaningless);
+ *   dist  (B,H,W) float32  float32(sqrt(float64(dist2))), inf where dist2 == -1;
+ *   out8  (B,H,W) uint8    with base (B,H,W) uint8: a site keeps base; any other pixel is a hit if dist2 <= t (greater == 0: it lies in
+ *                          the dilation of the sites by the disk dy^2 + dx^2 <= t) or if dist2 > t (greater != 0: it survives the erosion
+ *                          by that disk, the sites being the set's complement), -1 counting as infinitely far; a hit writes v_hit, a
+ *                          miss v_miss, and a value of -1 means "keep base".  out8 may be base itself.                                    */
+int cmu_edt_columns(const uint8_t* src, int cls, int border, int32_t* g, int B, int H, int W, void* stream);
+int cmu_edt_rows(const int32_t* g, int32_t* dist2, float* dist, const uint8_t* base, uint8_t* out8, int greater, int t, int v_hit,
+                 int v_miss, int B, int H, int W, void* stream);
+/* border (B,H,W) uint8: 1 on the border pixels of the rule's set (as above), else 0.                                                     */
+int cmu_surface_border(const uint8_t* src, int cls, uint8_t* border, int B, int H, int W, void* stream);
+/* Over the border pixels of src's set, with dist2 the transform to ANOTHER set's border: sums (B,2) fp64 = (sum of sqrt(dist2), added
+ * in a fixed order; sqrt(max dist2), 0 when n == 0); counts (B,3) int32 = (n border pixels, max dist2, number with dist2 <= tol2).
+ * max is -1 when n == 0 and 2^31 - 1 when dist2 is -1 (the other border is empty: both sums are then inf).  masked (B,H,W) int32, or
+ * NULL: dist2 on the border pixels, -2 elsewhere.  One workgroup per image.                                                             */
+int cmu_surface_reduce(const uint8_t* src, int cls, const int32_t* dist2, int tol2, int32_t* masked, double* sums, int32_t* counts, int B,
+                       int H, int W, void* stream);
+/* Exact order statistics: values (B,n_ranks) int32 = the ranks[b][r]-th smallest (from 0) of the non-negative entries of masked_a and
+ * masked_b of image b together, -1 if there are not that many (or the rank is negative); roots (B,n_ranks) fp64 = sqrt(value), inf
+ * for -1.  n_ranks is 1 or 2; ranks (B,n_ranks) int32 lives on the device.  Bisection on the value, one counting pass per step, at
+ * most 33 passes per rank; one workgroup per image.                                                                                     */
+int cmu_surface_select(const int32_t* masked_a, const int32_t* masked_b, const int32_t* ranks, int n_ranks, int32_t* values, double* roots,
+                       int B, int H, int W, void* stream);
+
 /* ---- image preprocessing (csrc/preprocess.hip): the reference's data_processing/pre_processing.py -------------
  * Planes are contiguous (B,H,W), 1 <= B <= 65535, H, W >= 1, H * W < 2^31; x is uint8 (is_u8 = 1) or float32 (is_u8 = 0).  Every kernel is
  * deterministic (fixed summation order, no float atomics).  `stats` is (B,4) float64 per image: mean, population standard deviation
