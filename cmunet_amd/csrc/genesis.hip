@@ -9,6 +9,7 @@
 //                               wins, atomicMax of the block number); per-(image, row segment) min / max of x
 //   cmu_genesis_bezier          the two sampled cubics (100,000 points, fp64), sorted without a general sort: a cubic's samples form
 //                               a few monotone runs (3 in exact arithmetic); runs are found on the device and merged by rank
+//                               (more than GEN_MAX_RUNS runs -- a near-constant image -- fall back to a general sort)
 //   cmu_genesis_intensity_paint np.interp through the table (fp64) and in- / out-painting
 //   cmu_genesis_mae             y = src[idx], x = y * (1 - mask)
 //   cmu_mse_fwd_bwd             nn.MSELoss()(logits[:, 0], y) + its gradient, fixed-order reduction
@@ -36,7 +37,7 @@ static_assert(sizeof(GenesisRec) == 112, "GenesisRec layout");
 enum { GF_FLIP0 = 1, GF_FLIP1 = 2, GF_LOCAL = 4, GF_NONLIN = 8, GF_SORTY = 16 };
 constexpr int GEN_NBLOCKS = 10000;
 constexpr int GEN_NT = 100000;          // Bezier samples
-constexpr int GEN_MAX_RUNS = 16;        // monotone runs a sampled cubic may show before the error word is set
+constexpr int GEN_MAX_RUNS = 16;        // monotone runs the rank merge handles; more go to gen_sort_general
 constexpr int GEN_OWNER_WORDS = 32768;  // LDS owner map (128 KB)
 constexpr int GEN_MAX_SLOT = 256;       // permutation indices are bytes
 constexpr int GEN_MAX_B = 1024;
@@ -293,6 +294,44 @@ __device__ static inline double gen_bezier(const double* P, int k) {
 // does a run's element `val` sit below v?  (ties: strict for runs after the element's own, non-strict for runs before it)
 __device__ static inline bool gen_below(double val, double v, bool strict) { return strict ? val < v : val <= v; }
 
+// More than GEN_MAX_RUNS runs (a near-constant image: the samples are rounding noise around one value): a general sort of the table by
+// the one workgroup, in place in `sorted` (no scratch).  A bitonic network over the next power of two in its all-ascending form -- the
+// first step of a merge compares mirrored partners, the later ones partners at a fixed distance -- so every comparator leaves the
+// smaller value at the lower index: the padding above GEN_NT, +inf in thought, never moves, and a comparator that touches it is skipped.
+// The comparators of one step are disjoint: each thread loads GEN_SORT_U pairs before it stores any.
+constexpr int GEN_SORT_N = 131072;
+constexpr int GEN_SORT_U = 8;
+static_assert(GEN_SORT_N >= GEN_NT && GEN_SORT_N / 2 < GEN_NT && (GEN_SORT_N / 2) % (1024 * GEN_SORT_U) == 0, "bitonic padding");
+__device__ static void gen_sort_general(const double* __restrict__ raw, double* __restrict__ sorted, int tid) {
+    for (int k = tid; k < GEN_NT; k += 1024) sorted[k] = raw[k];
+    __syncthreads();
+    for (int k = 2; k <= GEN_SORT_N; k <<= 1)
+        for (int j = k >> 1; j > 0; j >>= 1) {
+            const bool mirrored = j == (k >> 1);
+            for (int t0 = tid; t0 < GEN_SORT_N / 2; t0 += 1024 * GEN_SORT_U) {
+                int lo[GEN_SORT_U], hi[GEN_SORT_U];
+                double a[GEN_SORT_U], b[GEN_SORT_U];
+#pragma unroll
+                for (int q = 0; q < GEN_SORT_U; ++q) {
+                    const int t = t0 + 1024 * q;
+                    lo[q] = ((t & ~(j - 1)) << 1) | (t & (j - 1));
+                    hi[q] = mirrored ? lo[q] ^ (k - 1) : lo[q] + j;
+                    if (hi[q] < GEN_NT) {
+                        a[q] = sorted[lo[q]];
+                        b[q] = sorted[hi[q]];
+                    }
+                }
+#pragma unroll
+                for (int q = 0; q < GEN_SORT_U; ++q)
+                    if (hi[q] < GEN_NT && a[q] > b[q]) {
+                        sorted[lo[q]] = b[q];
+                        sorted[hi[q]] = a[q];
+                    }
+            }
+            __syncthreads();
+        }
+}
+
 __global__ __launch_bounds__(1024) void genesis_bezier_kernel(const GenesisRec* __restrict__ recs, const float* __restrict__ minmax,
                                                              int nseg, double* __restrict__ ws, int* __restrict__ err) {
     __shared__ int nbnd;
@@ -345,8 +384,8 @@ __global__ __launch_bounds__(1024) void genesis_bezier_kernel(const GenesisRec* 
     }
     __syncthreads();
     const int nb = nbnd;
-    if (nb + 1 > GEN_MAX_RUNS) {
-        if (tid == 0) atomicOr(err, 1);
+    if (nb + 1 > GEN_MAX_RUNS) {                                // (uniform: every thread reads the same count)
+        gen_sort_general(raw, sorted, tid);
         return;
     }
     if (tid == 0) {

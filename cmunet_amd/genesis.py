@@ -252,11 +252,12 @@ class GenesisPairGenerator:
         return out
 
     def check(self, err=None):
-        """Raise if a sampled cubic ever showed more monotone runs than the Bezier merge handles.  ``err``: the error word already read
-        back by the caller (else it is read here, which synchronises)."""
+        """Raise if the Bezier rank merge ever computed a position outside its table (bit 1 of the error word; any number of monotone
+        runs is sorted, so bit 0 is no longer raised).  ``err``: the error word already read back by the caller (else it is read here,
+        which synchronises)."""
         e = int(self.err.item()) if err is None else int(err)
         if e:
-            raise RuntimeError(f"cmu_genesis_bezier: error word {e:#x} (a sampled cubic showed more than 16 monotone runs)")
+            raise RuntimeError(f"cmu_genesis_bezier: error word {e:#x} (the Bezier merge ranked a sample outside its table)")
 
 
 # ------------------------------------------------------------------------------------------------

@@ -814,8 +814,9 @@ int cmu_genesis_sample(void* recs, int16_t* blocks, uint8_t* perms, int N, int B
 /* y = flip(src[rec.src]) (src (N,H,W) f32); x = local pixel shuffle of y (last covering block wins); minmax (B, segments, 2) f32 */
 int cmu_genesis_gather_shuffle(const float* src, const void* recs, const int16_t* blocks, const uint8_t* perms, float* x, float* y,
                                float* minmax, int B, int H, int W, void* stream);
-/* both sampled cubics of nonlinear_transformation (fp64, 100,000 points) and their sorted copies in ws; a cubic whose samples show
- * more than 16 monotone runs sets bit 0 of *err, a rank outside the table bit 1 (device word, read at the next synchronisation). */
+/* both sampled cubics of nonlinear_transformation (fp64, 100,000 points) and their sorted copies in ws, for any number of monotone
+ * runs (up to 16: merged by rank; more -- a near-constant image, whose samples are rounding noise -- a general sort in place).  A rank
+ * outside the table sets bit 1 of *err (device word, read at the next synchronisation); bit 0 is no longer raised.               */
 int64_t cmu_genesis_bezier_ws_bytes(int B);
 int cmu_genesis_bezier(const void* recs, const float* minmax, int B, int H, int W, void* ws, int* err, void* stream);
 /* x <- np.interp(x, xs, ys) (fp64) where the record asks for it, then in- / out-painting; noise (B,H,W) f32 or NULL (Philox).  */

@@ -68,6 +68,60 @@ def test_mae_replay_reproduces_reference(fix):
     assert (x.view(np.int32) == case["x"].view(np.int32)).all()
 
 
+def test_bezier_kernel_order_agrees_with_reference_order():
+    """The kernel's evaluation order against bezier_curve's (np.dot over the four Bernstein rows), per element, within
+    16 * 2^-53 * max|P_i|: each Bernstein term carries at most 4 roundings (the power included), its product with P_i and the three
+    additions at most 4 more, against terms that sum to at most max|P_i| -- 8 u per evaluation, and two evaluations are compared."""
+    for group, name, mn, mx, bez, _, _ in R.BEZIER_CASES:
+        cx, cy = R.controls(mn, mx, bez)
+        rx, ry = R.bezier([[cx[i], cy[i]] for i in range(4)])
+        for P, ref in ((cx, rx), (cy, ry)):
+            bound = 16 * 2.0 ** -53 * np.abs(P).max()
+            err = np.abs(R.bezier_kernel_order(P) - ref).max()
+            assert err <= bound, (group, name, err / bound)
+
+
+def test_controls_round_in_float32():
+    cx, cy = R.controls(np.float32(-1.7), np.float32(2.9), (0.3, 0.6, 0.2, 0.9))
+    d = np.float32(np.float32(2.9) - np.float32(-1.7))
+    assert cx[1] == np.float32(np.float32(np.float32(0.3) * d) + np.float32(-1.7)) and cy[2] == np.float32(np.float32(np.float32(0.9) * d) + np.float32(-1.7))
+    assert cx[0] == cy[0] == np.float32(-1.7) and cx[3] == cy[3] == np.float32(2.9) and cx.dtype == np.float64
+    # a range of two float32 steps: 0.6 * 2 steps rounds to one step, 0.9 * 2 steps to two
+    cx, cy = R.controls(R.ulp32(0.75, 0), R.ulp32(0.75, 2), (0.3, 0.6, 0.2, 0.9))
+    assert cy.tolist() == [0.75, float(R.ulp32(0.75, 1)), float(R.ulp32(0.75, 2)), float(R.ulp32(0.75, 2))]
+
+
+def test_runs_counts_sign_changes_of_nonzero_differences():
+    assert R.runs([1.0, 2.0, 3.0])[0] == 1 and R.runs([3.0, 3.0, 3.0])[0] == 1 and R.runs([5.0])[0] == 1
+    n, b = R.runs([0.0, 1.0, 1.0, 0.5, 0.5, 0.5, 2.0, 1.0])
+    assert n == 4 and b.tolist() == [3, 6, 7]          # the flat stretch belongs to the run it sits in
+    n, b = R.runs([2.0, 2.0, 1.0, 1.0, 3.0])
+    assert n == 2 and b.tolist() == [4]
+
+
+def test_bezier_cases_fall_in_their_run_categories():
+    """Every case of the shared table, on the restatement: one run, 2 .. 16 (the kernel's merge across runs) or more than 16 (its
+    general sort).  The seam cases have a run that starts where the table says, counted in the kernel's 98-sample chunks."""
+    for group, name, mn, mx, bez, cat_x, cat_y in R.BEZIER_CASES:
+        for P, cat in zip(R.controls(mn, mx, bez), (cat_x, cat_y)):
+            n, b = R.runs(R.bezier_kernel_order(P))
+            assert R.in_category(n, cat), (group, name, n, cat)
+            if group == "three" and cat == "few":
+                assert n == 3, (name, n)
+            if group == "seam" and cat == "few":
+                assert n == 3 and int(name) in (b % R.CHUNK).tolist(), (name, b)
+    assert {c[0] for c in R.BEZIER_CASES} == {"ordinary", "three", "seam", "fewulp", "overflow"}
+
+
+def test_in_range_draws_give_one_run():
+    """Why the kernel tests need hand-made records: with draws in [0, 1), as the sampler and the reference's random.random() give them,
+    the cubic is monotone, so the sorter only ever sees a table that is sorted already (or reversed)."""
+    rng = np.random.RandomState(11)
+    for bez in rng.random_sample((1000, 4)):
+        for P in R.controls(np.float32(-1.7), np.float32(2.9), bez):
+            assert R.runs(R.bezier_kernel_order(P))[0] == 1, bez
+
+
 def test_record_layout_is_112_bytes():
     assert G.REC_DTYPE.itemsize == 112
     assert G.REC_DTYPE.fields["bez"][1] == 80 and G.REC_DTYPE.fields["block_off"][1] == 64

@@ -1060,14 +1060,19 @@ def test_genesis_bezier(ops):
     """cmu_genesis_bezier fills the workspace with the batch's Bezier tables and cmu_genesis_intensity_paint reads them: the pair is held
     together, against the restatement of the batch's own records (test_gpu_genesis.py::test_device_batch_equals_restatement_of_its_records:
     bit for bit without the nonlinear transform, 2 ulp with it, painted pixels in [0, 1]).  x is transformed in place (run() loads the
-    gather / shuffle output first); the error word is OR-ed into."""
+    gather / shuffle output first); the error word is OR-ed into.  The last case is a batch of a constant 0.75 image and an image of two
+    neighbouring float32 values with nonlinear_rate = 1: their sampled cubics are rounding noise with far more than 16 monotone runs, so
+    the tables go through the kernel's general sort, which works in place in the workspace."""
     import genesis_restate as GR
     from cmunet_amd import genesis as G
     from test_gpu_genesis import _cfg, ulps
     cases = []
-    for B, H, N, seed in ((16, 64, 32, 9), (3, 48, 5, 2), (1, 42, 1, 4)):
+    for B, H, N, seed, flat in ((16, 64, 32, 9, False), (3, 48, 5, 2, False), (1, 42, 1, 4, False), (2, 42, 2, 6, True)):
         src = np.random.RandomState(1).standard_normal((N, H, H)).astype(np.float32)
-        gen_ = G.GenesisPairGenerator(src, B, _cfg(), seed=seed, offset=3, device=DEV)
+        if flat:
+            src[0] = 0.75
+            src[1] = np.where(src[1] > 0, np.nextafter(np.float32(1), np.float32(2)), np.float32(1))
+        gen_ = G.GenesisPairGenerator(src, B, _cfg(rates={"nonlinear_rate": 1.0} if flat else None), seed=seed, offset=3, device=DEV)
         p = ops._p
         call("cmu_genesis_sample", p(gen_.recs), p(gen_.blocks), p(gen_.perms), gen_.N, B, H, H, 0, *(float(v) for v in (gen_.config.flip_rate, gen_.config.local_rate,
              gen_.config.nonlinear_rate, gen_.config.paint_rate, gen_.config.inpaint_rate)), gen_.seed, gen_.offset, ops._stream())
@@ -1083,7 +1088,8 @@ def test_genesis_bezier(ops):
             call("cmu_genesis_bezier", p(ins["recs"]), p(ins["minmax"]), *a, p(ws), p(o["err"]), ops._stream())
             call("cmu_genesis_intensity_paint", p(ins["recs"]), p(ws), None, gen_.seed, gen_.offset, p(o["x"]), *a, ops._stream())
 
-        def check(o, rx=rx, rec=rec, B=B):
+        def check(o, rx=rx, rec=rec, B=B, flat=flat):
+            assert not flat or all(int(f) & G.GF_NONLIN for f in rec["recs"]["flags"])
             x = o["x"].cpu().numpy()
             painted = np.isnan(rx)
             assert int(o["err"].item()) == 0 and ((x[painted] >= 0) & (x[painted] <= 1)).all()
@@ -1093,7 +1099,7 @@ def test_genesis_bezier(ops):
                     assert ulps(x[b][keep], rx[b][keep]).max() <= 2, b
                 else:
                     assert (x[b][keep].view(np.int32) == rx[b][keep].view(np.int32)).all(), b
-        cases.append((Case(f"{B}x{H}x{H}", lib().cmu_genesis_bezier_ws_bytes(B),
+        cases.append((Case(f"{B}x{H}x{H}" + (" near-constant" if flat else ""), lib().cmu_genesis_bezier_ws_bytes(B),
                            {"x": Out((B, H, H), prefill=0.0, accumulates=True, why="transformed in place; run() loads the gather / shuffle output first"),
                             "err": Out((1,), I32, prefill=0, accumulates=True, why="the error word is OR-ed into")}, ins, DEV, "f32", 2 * B, False), run, check))
     hold("genesis_bezier + intensity_paint", cases)
