@@ -229,6 +229,9 @@ _SIGS = {
     "cmu_pre_unsharp_cols": (_I, [_P, _I, _F, _P, _P, _I, _F, _I, _P, _P, _I, _I, _I, _P]),
     "cmu_pre_crop": (_I, [_P, _I, _P, _I, _I, _I, _I, _I, _I, _I, _P]),
     "cmu_pre_integrate_masks": (_I, [_P, _P, _I, _I, _L, _P]),
+    "cmu_prob_hist": (_I, [_P, _I, _P, _I, _P, _P, _P, _I, _I, _I, _I, _I, _I, _I, _P]),
+    "cmu_hist_curves": (_I, [_P, _P, _I, _I, _D, _D, _I, _P, _P, _P, _P]),
+    "cmu_threshold_mask": (_I, [_P, _F, _I, _I, _P, _L, _P]),
     "cmu_amp_state_bytes": (_I, []),
     "cmu_amp_init": (_I, [_P, _F, _P]),
     "cmu_amp_check_finite": (_I, [_P, _L, _P, _P]),

@@ -5,6 +5,7 @@
 // These are latency/HBM-bound: one pass per tensor, wave64 shuffle reductions (block_sum / block_sum_d / block_max, common.h),
 // fixed-order final sums.
 #include "common.h"
+#include "seg_softmax.h"
 
 // ---------------------------------------------------------------------------------------------
 // masked MSE: ws = [rows][4] floats (mean, rstd, num, den) + [2] (loss, den_total)
@@ -300,30 +301,7 @@ __device__ static inline int64_t seg_group_base(int64_t g, int64_t gpi, bool sma
     }
     return b * K * HW + r * V;
 }
-// softmax of one pixel in fp32: p[c] = e^(l[c] - max) / sum, lse = max + log(sum); classes >= K are left alone
-template <int KT>
-__device__ static inline void seg_softmax(const float (&l)[KT], int K, float (&p)[KT], float& lse) {
-    float m = l[0];
-#pragma unroll
-    for (int c = 1; c < KT; ++c)
-        if (c < K) m = fmaxf(m, l[c]);
-    float se = 0.f;
-#pragma unroll
-    for (int c = 0; c < KT; ++c)
-        if (c < K) {
-            // e^(l - m) with the rounding d of the fp32 difference given back (e^(x + d) = e^x (1 + d)): a class far below the
-            // maximum would otherwise carry |l - m| roundoffs in its probability, and through sum_c p_c G_c into every gradient
-            const float x = l[c] - m;
-            const float d = (float)(((double)l[c] - (double)m) - (double)x);
-            const float e = expf(x);
-            p[c] = fmaf(e, d, e);
-            se += p[c];
-        }
-    lse = m + logf(se);
-#pragma unroll
-    for (int c = 0; c < KT; ++c)
-        if (c < K) p[c] = p[c] / se;
-}
+// seg_softmax<KT> (the pixel's fp32 softmax): seg_softmax.h, shared with the probability histogram of prob_hist.hip
 
 template <int KT, int V, typename TY>
 __global__ __launch_bounds__(256) void seg_stats_kernel(const float* __restrict__ logits, const TY* __restrict__ y,

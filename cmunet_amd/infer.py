@@ -3,7 +3,9 @@
   load_segmentation_model(path_or_state, dtype, device)   a pickled module, a state dict, or a path to either -> UNet on the GPU
   Segmenter(model, size=256, batch=32, ...).segment(images)   images of any size -> uint8 masks at the images' own sizes
   segment_files(model, paths, out_dir)                    ``.npy`` images -> ``<stem>_mask.npy``
+  calibrate_threshold(segmenter, images, masks)           the threshold of ``Segmenter(threshold=, threshold_class=)`` from a validation split
   python -m cmunet_amd.infer --model M --images DIR --out DIR [--size 256] [--batch 32] [--dtype f16] [--threshold 0.5]
+                              [--threshold-class C]
                               [--tile 256 [--stride 128] [--window gaussian] [--pad reflect]] [--tta d4]
                               [--min-size 50] [--keep-largest 2] [--fill-holes] [--connectivity 8] [--opening R] [--closing R]
                               [--crop 475] [--unsharp RADIUS AMOUNT [--preserve-range]] [--normalize {none,intensity,minmax,rows}]
@@ -143,11 +145,26 @@ class Segmenter:
     ``preprocess`` (None: the calls above run exactly as before): a callable ``(n,H,W) uint8 / float32 device batch -> (n,H',W')`` --
     ``preprocess.Preprocess`` -- applied to every chunk before the resize / tiling.  Masks (and ``min_size``) are then at the
     preprocessed size H' x W', e.g. the cropped one, not the raw image's; the ``size=None`` multiple-of-2**(depth-1) rule applies to
-    H' x W'."""
+    H' x W'.
+
+    ``threshold_class`` (None: the calls above run exactly as before, the same bits): for a head of K >= 2 classes the mask is class C =
+    ``threshold_class`` where the probability of class C exceeds ``threshold`` and class 0 elsewhere, instead of the argmax (on the tiled
+    path the BLENDED probability): that class's probability is requested internally and ``ops.threshold_mask`` runs before the resize back
+    and the clean-up; ``class_values`` and the clean-up apply as before.  ``calibrate_threshold`` picks the threshold.  ValueError for a
+    one-channel head (its ``threshold`` already applies), C outside 1..K-1, and ``segment(prob_class=)`` naming another class."""
 
     def __init__(self, model, size=256, batch=32, threshold=0.5, class_values=None, tile=None, stride=None, window="gaussian",
-                 pad="reflect", tta=None, min_size=None, keep_largest=None, fill_holes=False, connectivity=8, preprocess=None, opening=None, closing=None):
+                 pad="reflect", tta=None, min_size=None, keep_largest=None, fill_holes=False, connectivity=8, preprocess=None, opening=None, closing=None,
+                 threshold_class=None):
         self.model, self.size, self.batch, self.threshold = model, size, int(batch), threshold
+        self.threshold_class = None
+        if threshold_class is not None:
+            K = int(model.conv_last.weight.shape[0])
+            if K < 2:
+                raise ValueError("Segmenter: threshold_class is for a head of two or more classes; a one-channel head's threshold already applies")
+            if isinstance(threshold_class, bool) or int(threshold_class) != threshold_class or not 1 <= int(threshold_class) <= K - 1:
+                raise ValueError(f"Segmenter: threshold_class must lie in 1..{K - 1}, got {threshold_class!r}")
+            self.threshold_class = int(threshold_class)
         self.mult = 1 << (_depth(model) - 1)
         if size is not None and (int(size) <= 0 or int(size) % self.mult):
             raise ValueError(f"Segmenter: size={size} must be a positive multiple of {self.mult} (UNet depth {_depth(model)})")
@@ -249,12 +266,22 @@ class Segmenter:
                             prob_class or 0, self.threshold, self._table(x.device))
         return labels, prob
 
+    def _threshold_class_mask(self, prob):
+        """Class ``threshold_class`` where its probability exceeds the threshold, class 0 elsewhere -- as class values when the head
+        would have written them (no clean-up behind it)."""
+        C = self.threshold_class
+        v = self.class_values if self.class_values is not None and not self.post else None
+        return ops.threshold_mask(prob, self.threshold, C if v is None else v[C], 0 if v is None else v[0])
+
     def _chunk(self, src, prob_class=None):
         """src (n,H,W) float32 / uint8 on the device -> (n,H,W) uint8, or (labels, prob) with ``prob_class`` (prob at the size the
         network ran at).  Launches only: no host synchronisation."""
         H, W = src.shape[1:]
         S = self.size
         x = src if S is None or (H, W) == (S, S) else ops.resize_bicubic(src, S, S)
+        want_prob = prob_class is not None
+        if self.threshold_class is not None:
+            prob_class = self.threshold_class
         if self.tiled:
             lab, prob = self._chunk_tiled(x, prob_class)
         else:
@@ -262,6 +289,10 @@ class Segmenter:
                 x = x.float()
             lab = self.model.predict(x, threshold=self.threshold, prob_class=prob_class, class_values=self._table(src.device))
             lab, prob = lab if prob_class is not None else (lab, None)
+        if self.threshold_class is not None:
+            lab = self._threshold_class_mask(prob)
+            if not want_prob:
+                prob_class = prob = None
         lab = lab if tuple(lab.shape[1:]) == (H, W) else ops.resize_nearest(lab, H, W)
         if self.post:      # on the mask at the image's own size: min_size counts source pixels
             K = max(int(self.model.conv_last.weight.shape[0]), 2)
@@ -279,6 +310,8 @@ class Segmenter:
         if prob_class is not None and not 0 <= int(prob_class) < K1:
             raise ValueError(f"Segmenter.segment: prob_class {prob_class} outside 0..{K1 - 1}")
         prob_class = None if prob_class is None else int(prob_class)
+        if self.threshold_class is not None and prob_class not in (None, self.threshold_class):
+            raise ValueError(f"Segmenter.segment: prob_class {prob_class} is not the threshold_class {self.threshold_class} of this Segmenter")
         dev = self.model.conv_last.weight.device
         if dev.type != "cuda":
             raise RuntimeError("Segmenter: the model must live on a CUDA/ROCm device; there is no CPU fallback in this package")
@@ -331,6 +364,35 @@ def segment_files(model, paths, out_dir, **kw):
     return written
 
 
+def calibrate_threshold(segmenter, images, masks, cls=1, bins=256, score="dice", beta=1.0):
+    """The threshold of class ``cls`` that maximises ``score`` ('dice': F-beta with ``beta``, 'iou', 'youden') over a validation split:
+    ``segmenter.segment(images, prob_class=cls)``; every uint8 label mask brought to its probability's size (the size the network ran at)
+    with ``ops.resize_nearest``, the training pipeline's rule; ONE histogram pooled over all images, of any mix of sizes, on the device;
+    ``metrics.best_threshold``.  Returns (threshold, sweep): the threshold j / bins as a Python float -- the single host synchronisation
+    -- which lies inside (0, 1) and is valid for ``Segmenter(threshold=, threshold_class=cls)`` (one-channel head: ``threshold=``), and the
+    ``metrics.threshold_sweep`` of the pooled histogram.  The sweep describes the probabilities (see ``metrics.threshold_sweep``)."""
+    from . import metrics
+    bins = ops.check_bins("calibrate_threshold", bins)
+    items = list(images.unbind(0)) if torch.is_tensor(images) and images.dim() == 3 else list(images)
+    labels = list(masks.unbind(0)) if torch.is_tensor(masks) and masks.dim() == 3 else list(masks)
+    if not items or len(items) != len(labels):
+        raise ValueError(f"calibrate_threshold: {len(items)} images for {len(labels)} masks")
+    res = segmenter.segment(items, prob_class=cls)
+    hist = None
+    for (_, prob), m in zip(res, labels):
+        m = m if torch.is_tensor(m) else torch.from_numpy(np.ascontiguousarray(m))
+        if m.dtype != torch.uint8 or m.dim() != 2:
+            raise ValueError(f"calibrate_threshold: every mask must be a 2-D uint8 label map, got {tuple(m.shape)} {m.dtype}")
+        m = m.to(prob.device)[None].contiguous()
+        if tuple(m.shape[1:]) != tuple(prob.shape):
+            m = ops.resize_nearest(m, prob.shape[0], prob.shape[1])
+        # the one probability plane's "foreground" (label != 0): the pixels of class cls (a one-channel head: every non-zero label)
+        y = m if int(segmenter.model.conv_last.weight.shape[0]) < 2 else (m == int(cls)).to(torch.uint8)
+        hist = metrics.prob_histogram(prob[None].contiguous(), y, bins, None, pooled=True, out=hist)
+    thr, _ = metrics.best_threshold(hist, 0, score, beta)
+    return float(thr.item()), metrics.threshold_sweep(hist, beta=beta, score=score)
+
+
 def build_parser():
     ap = argparse.ArgumentParser(prog="python -m cmunet_amd.infer", description="Segment .npy images with a finetuned UNet on the GPU.")
     ap.add_argument("--model", required=True, help="best_model.pth of train() (a pickled module) or a state-dict file")
@@ -341,6 +403,8 @@ def build_parser():
     ap.add_argument("--batch", type=int, default=32)
     ap.add_argument("--dtype", default="f32", choices=["f32", "f16", "bf16"], help="storage type of the activations")
     ap.add_argument("--threshold", type=float, default=0.5, help="probability threshold of a one-channel head")
+    ap.add_argument("--threshold-class", type=int, default=None, metavar="C",
+                    help="K >= 2 classes: the mask is class C where its probability exceeds --threshold, class 0 elsewhere (not the argmax)")
     ap.add_argument("--tile", type=int, default=None, help="sliding-window inference with square tiles of this side (any image size)")
     ap.add_argument("--stride", type=int, default=None, help="step of the sliding window (default tile // 2)")
     ap.add_argument("--window", default="gaussian", choices=list(WINDOWS), help="weights of a tile's pixels where tiles overlap")
@@ -375,7 +439,7 @@ def main(argv=None):
     written = segment_files(model, paths, args.out, size=size, batch=args.batch, threshold=args.threshold, tile=args.tile,
                             stride=args.stride, window=args.window, pad=args.pad, tta=None if args.tta == "none" else args.tta,
                             min_size=args.min_size, keep_largest=args.keep_largest, fill_holes=args.fill_holes, connectivity=args.connectivity,
-                            preprocess=pre, opening=args.opening, closing=args.closing)
+                            preprocess=pre, opening=args.opening, closing=args.closing, threshold_class=args.threshold_class)
     print(f"{len(written)} masks written to {args.out}")
     return 0
 

@@ -30,6 +30,9 @@ raises), ``weight`` / ``pos_weight`` are one element or per channel ((C,1,1) / (
 of int64 / int32 / uint8 / fp32 / fp64, read in their own dtype: 1-8 bytes per pixel instead of the 8K of fp64 one-hot planes) and
 ``NLLLoss(activation, ignore_channels, threshold)`` one-hot targets whose arg-max over the kept channels is taken in the kernel; both run
 on ``cmu_index_ce_fwd`` / ``_bwd`` (2..8 classes), which yield three fp64 sums from which torch's reductions follow on the device.
+Choosing the threshold (no reference counterpart): ``prob_histogram`` -- one pass of ``cmu_prob_hist`` -- then
+``threshold_sweep`` / ``best_threshold`` (``cmu_hist_curves``: every threshold j / bins at once) and the threshold-free ``Metric``s
+``AUROC``, ``AveragePrecision``, ``CalibrationError``.  New names only: every class above keeps its configuration checks.
 """
 import collections
 import math
@@ -1071,3 +1074,151 @@ class RobustCrossEntropyLoss(Loss):
         if self.reduction == "mean":
             return t[0] / t[1] if e == 0.0 else (1.0 - e) * t[0] / t[1] + (e / K) * t[2] / t[1]
         return t[0] if e == 0.0 else (1.0 - e) * t[0] + (e / K) * t[2]
+
+
+# ---------------------------------------------------------------------------------------------
+# Choosing the operating point: one histogram pass (csrc/prob_hist.hip), then every threshold j / bins at once (csrc/hist_curves.h)
+# ---------------------------------------------------------------------------------------------
+class ProbHistogram:
+    """``counts`` (Bout,K,2,bins+1) int64: pixels by row (image or pool, class), ground truth and bin; ``conf`` (Bout,K,bins+1) uint64: the
+    bin's sum of floor(p * 2**32); ``invalid`` (Bout,K) int32: probabilities that were NaN or outside [0, 1]; ``bins``."""
+
+    def __init__(self, counts, conf, invalid, bins):
+        self.counts, self.conf, self.invalid, self.bins = counts, conf, invalid, int(bins)
+
+    def __iter__(self):
+        return iter((self.counts, self.conf, self.invalid, self.bins))
+
+
+_HIST_ACTIVATIONS = ("softmax", "softmax2d", "sigmoid", None)
+
+
+def prob_histogram(y_pr, y_gt, bins=256, activation="softmax", pooled=True, out=None):
+    """The probability histogram of a batch in ONE pass.  ``y_pr`` (B,K,H,W): logits with ``activation`` 'softmax' / 'softmax2d' (K >= 2;
+    the probability bits ``DiceMetric(threshold=)`` compares) or 'sigmoid' (K = 1), probability planes with ``None`` (what
+    ``UNet.predict_probs``, ``ops.softmax_planes`` or ``Segmenter.segment(prob_class=)`` give; a (B,H,W) tensor is one plane).  ``y_gt``:
+    one-hot float32 / float64 planes of y_pr's shape (positive iff > 0.5) or a (B,H,W) uint8 label map (class c positive for plane c; one
+    plane: label != 0).  ``bins``: a power of two in 2..1024; bin b holds (b-1)/bins < p <= b/bins, so the pixels above threshold j/bins
+    are the bins above j.  ``pooled``: one row set for the batch, else one per image.  ``out``: a ProbHistogram to add into (a whole
+    validation set, images of any sizes, pools without a host synchronisation)."""
+    if activation not in _HIST_ACTIVATIONS:
+        raise ValueError(f"prob_histogram: activation must be one of {_HIST_ACTIVATIONS}, got {activation!r}")
+    bins = ops.check_bins("prob_histogram", bins)
+    if not (torch.is_tensor(y_pr) and torch.is_tensor(y_gt)):
+        raise ValueError("prob_histogram: y_pr and y_gt are tensors")
+    if not y_pr.is_cuda or not y_gt.is_cuda:
+        raise RuntimeError("prob_histogram: the HIP path needs CUDA/ROCm tensors (no CPU fallback)")
+    if y_pr.dim() == 3 and activation is None:
+        y_pr = y_pr[:, None]
+        if y_gt.dim() == 3 and y_gt.dtype != torch.uint8:
+            y_gt = y_gt[:, None]
+    if y_pr.dim() != 4 or not 1 <= y_pr.shape[1] <= ops.HIST_MAX_K:
+        raise ValueError(f"prob_histogram: y_pr must be (B,K,H,W) with 1 <= K <= {ops.HIST_MAX_K}, got {tuple(y_pr.shape)}")
+    B, K, H, W = y_pr.shape
+    if activation in ("softmax", "softmax2d") and K < 2:
+        raise ValueError("prob_histogram: a softmax needs K >= 2 planes; a one-channel head takes activation='sigmoid'")
+    if activation == "sigmoid" and K != 1:
+        raise ValueError(f"prob_histogram: activation='sigmoid' is the one-channel head's; got K = {K}")
+    if y_gt.dtype == torch.uint8:
+        if tuple(y_gt.shape) != (B, H, W):
+            raise ValueError(f"prob_histogram: a uint8 label map must be (B,H,W) = {(B, H, W)}, got {tuple(y_gt.shape)}")
+    elif y_gt.dtype in (torch.float32, torch.float64):
+        if tuple(y_gt.shape) != (B, K, H, W):
+            raise ValueError(f"prob_histogram: one-hot targets must have y_pr's shape {(B, K, H, W)}, got {tuple(y_gt.shape)}")
+    else:
+        raise ValueError(f"prob_histogram: y_gt must be float32 / float64 one-hot planes or a uint8 label map, got {y_gt.dtype}")
+    Bout = 1 if pooled else B
+    if out is None:
+        counts, conf, invalid = ops.hist_buffers(Bout, K, bins, y_pr.device)
+        out = ProbHistogram(counts, conf, invalid, bins)
+        accumulate = False
+    else:
+        if not isinstance(out, ProbHistogram) or out.bins != bins or tuple(out.counts.shape) != (Bout, K, 2, bins + 1):
+            raise ValueError(f"prob_histogram: out must be a ProbHistogram of {bins} bins with counts {(Bout, K, 2, bins + 1)}")
+        accumulate = True
+    ops.prob_hist(y_pr.detach().float().contiguous(), y_gt.contiguous(), bins, activation is not None, out.counts, out.conf, out.invalid,
+                  pooled=pooled, accumulate=accumulate)
+    return out
+
+
+class ThresholdSweep:
+    """Device tensors of ``threshold_sweep``; the leading dimensions are the histogram's (Bout,K).  ``thresholds`` (bins+1,) float64 = j/bins;
+    ``tp fp fn tn`` (...,bins+1) int64; ``dice iou precision recall specificity`` (...,bins+1) float64; ``auroc average_precision ece mce``
+    (...) float64; ``best_j`` / ``best_value``: the argmax over j = 1..bins-1 of the selected score and its value."""
+
+
+_CURVE_NAMES = ("dice", "iou", "precision", "recall", "specificity")
+
+
+def _curves(hist, eps, beta, select):
+    if not isinstance(hist, ProbHistogram):
+        raise ValueError("expected the ProbHistogram prob_histogram returns")
+    return ops.hist_curves(hist.counts, hist.conf, eps=eps, beta=beta, select=select)
+
+
+def threshold_sweep(hist, eps=1e-7, beta=1.0, score="dice"):
+    """Every threshold j / bins of the histogram at once (cmu_hist_curves): the exact confusion counts -- at threshold j/bins the integers
+    ``DiceMetric(threshold=j/bins)`` / ``IoU`` count -- the reference's score formulas (metrics.py:135-198) with ``eps`` / ``beta``, and the
+    threshold-free AUROC, average precision, expected / maximum calibration error.  The sweep describes the PROBABILITIES; a one-channel
+    ``UNet.predict`` compares the logit with log(t / (1 - t)), which can differ from sigmoid > t at a probability on a bin edge."""
+    if score not in ops.HIST_SELECT:
+        raise ValueError(f"threshold_sweep: score must be one of {sorted(ops.HIST_SELECT)}, got {score!r}")
+    cum, scores, summary = _curves(hist, eps, beta, ops.HIST_SELECT[score])
+    s = ThresholdSweep()
+    s.bins = hist.bins
+    s.thresholds = torch.arange(hist.bins + 1, dtype=torch.float64, device=cum.device) / hist.bins
+    s.tp, s.fp, s.fn, s.tn = cum.unbind(-2)
+    for k, name in enumerate(_CURVE_NAMES):
+        setattr(s, name, scores.select(-2, k))
+    s.auroc, s.average_precision, s.ece, s.mce, s.best_j, s.best_value = summary.unbind(-1)
+    return s
+
+
+def best_threshold(hist, cls=1, score="dice", beta=1.0, eps=1e-7):
+    """(threshold, value): the threshold j / bins, 1 <= j <= bins - 1, that maximises ``score`` ('dice': F-beta, 'iou', 'youden') of class
+    ``cls`` on the pooled histogram (row 0), the first one on a tie, and that score -- 0-d float64 device tensors, no host synchronisation."""
+    if score not in ops.HIST_SELECT:
+        raise ValueError(f"best_threshold: score must be one of {sorted(ops.HIST_SELECT)}, got {score!r}")
+    if not isinstance(hist, ProbHistogram) or not 0 <= int(cls) < hist.counts.shape[1]:
+        raise ValueError(f"best_threshold: cls {cls!r} outside the histogram's classes")
+    _, _, summary = ops.hist_curves(hist.counts[0, int(cls)].contiguous(), hist.conf[0, int(cls)].contiguous(), eps=eps, beta=beta,
+                                    select=ops.HIST_SELECT[score])
+    return summary[4] / hist.bins, summary[5]
+
+
+class _HistMetric(Metric):
+    """A threshold-free score of class ``cls`` from the batch's pooled probability histogram: a float64 device scalar."""
+    _column = 0
+
+    def __init__(self, cls=1, bins=256, activation="softmax", **kwargs):
+        super().__init__(**kwargs)
+        if activation not in _HIST_ACTIVATIONS:
+            raise ValueError(f"{self.__name__}: activation must be one of {_HIST_ACTIVATIONS}, got {activation!r}")
+        if isinstance(cls, bool) or int(cls) != cls or not 0 <= int(cls) < ops.HIST_MAX_K:
+            raise ValueError(f"{self.__name__}: cls must lie in 0..{ops.HIST_MAX_K - 1}, got {cls!r}")
+        self.cls, self.bins, self.activation = int(cls), ops.check_bins(self.__name__, bins), activation
+
+    def forward(self, y_pr, y_gt):
+        hist = prob_histogram(y_pr, y_gt, self.bins, self.activation)
+        if self.cls >= hist.counts.shape[1]:
+            raise ValueError(f"{self.__name__}: cls {self.cls} outside the {hist.counts.shape[1]} classes of the prediction")
+        summary = ops.hist_curves(hist.counts[0, self.cls].contiguous(), hist.conf[0, self.cls].contiguous())[2]
+        return summary[self._column]
+
+
+class AUROC(_HistMetric):
+    """Area under the ROC curve of class ``cls`` over the batch's pixels (sklearn's roc_auc_score on the bin indices); NaN when a class is empty."""
+    __name__ = "auroc"
+    _column = 0
+
+
+class AveragePrecision(_HistMetric):
+    """sklearn's average_precision_score of class ``cls`` on the bin indices; NaN without a positive pixel."""
+    __name__ = "average_precision"
+    _column = 1
+
+
+class CalibrationError(_HistMetric):
+    """Expected calibration error of class ``cls``: sum over the bins of |positives - sum of probabilities| / pixels."""
+    __name__ = "ece"
+    _column = 2

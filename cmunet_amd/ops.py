@@ -1538,3 +1538,87 @@ def pre_integrate_masks(masks):
     out = torch.empty(B, H, W, dtype=torch.uint8, device=masks.device)
     call("cmu_pre_integrate_masks", _p(masks), _p(out), B, M, H * W, _stream())
     return out
+
+
+# probability histograms, threshold sweeps and calibration (csrc/prob_hist.hip, csrc/hist_curves.h)
+HIST_MAX_K = 8           # CMU_HIST_MAX_K
+HIST_MAX_BINS = 1024     # CMU_HIST_MAX_BINS
+HIST_SELECT = {"dice": 0, "fbeta": 0, "iou": 1, "youden": 2}
+_HIST_TARGET_KINDS = {torch.float32: 0, torch.float64: 1, torch.uint8: 2}
+
+
+def check_bins(what, bins):
+    if isinstance(bins, bool) or int(bins) != bins or not 2 <= int(bins) <= HIST_MAX_BINS or int(bins) & (int(bins) - 1):
+        raise ValueError(f"{what}: bins must be a power of two in 2..{HIST_MAX_BINS}, got {bins!r}")
+    return int(bins)
+
+
+def hist_buffers(rows_out, K, bins, device):
+    """Zeroed (counts (Bout,K,2,bins+1) int64, conf (Bout,K,bins+1) uint64, invalid (Bout,K) int32) of cmu_prob_hist."""
+    return (torch.zeros(rows_out, K, 2, bins + 1, dtype=torch.int64, device=device),
+            torch.zeros(rows_out, K, bins + 1, dtype=torch.int64, device=device).view(torch.uint64),
+            torch.zeros(rows_out, K, dtype=torch.int32, device=device))
+
+
+def prob_hist(src, target, bins, from_logits, counts, conf, invalid, pooled=True, accumulate=False):
+    """One pass of cmu_prob_hist: src (B,K,H,W) float32 logits (``from_logits``: the softmax of cmu_seg_stats_fwd, K = 1: the sigmoid)
+    or probability planes; ``target`` float32 / float64 planes of src's shape (positive iff > 0.5) or a (B,H,W) uint8 label map.
+    Adds into (``accumulate``) or overwrites counts / conf / invalid (``hist_buffers``'s shapes; Bout = 1 with ``pooled``, else B)."""
+    for t in (src, target, counts, conf, invalid):
+        if not t.is_cuda:
+            raise RuntimeError("prob_hist runs on the GPU only; there is no CPU fallback in this package")
+    bins = check_bins("prob_hist", bins)
+    if src.dim() != 4 or src.dtype != torch.float32 or not 1 <= src.shape[1] <= HIST_MAX_K or min(src.shape) < 1:
+        raise ValueError(f"prob_hist: src must be (B,K,H,W) float32 with 1 <= K <= {HIST_MAX_K}, got {tuple(src.shape)} {src.dtype}")
+    if not src.is_contiguous() or not target.is_contiguous():
+        raise ValueError("prob_hist: src and target must be contiguous")
+    B, K, H, W = src.shape
+    kind = _HIST_TARGET_KINDS.get(target.dtype)
+    if kind is None or tuple(target.shape) != ((B, H, W) if kind == 2 else (B, K, H, W)):
+        raise ValueError(f"prob_hist: the target is float32 / float64 planes of src's shape {tuple(src.shape)} or a (B,H,W) uint8 label "
+                         f"map, got {tuple(target.shape)} {target.dtype}")
+    Bout = 1 if pooled else B
+    for name, t, shape, dt in (("counts", counts, (Bout, K, 2, bins + 1), (torch.int64,)), ("conf", conf, (Bout, K, bins + 1), (torch.uint64, torch.int64)),
+                               ("invalid", invalid, (Bout, K), (torch.int32,))):
+        if tuple(t.shape) != shape or t.dtype not in dt or not t.is_contiguous():
+            raise ValueError(f"prob_hist: {name} must be a contiguous {shape} {dt[0]} tensor, got {tuple(t.shape)} {t.dtype}")
+    call("cmu_prob_hist", _p(src), int(bool(from_logits)), _p(target), kind, _p(counts), _p(conf), _p(invalid), B, K, H, W, bins,
+         int(bool(pooled)), int(bool(accumulate)), _stream())
+
+
+def hist_curves(counts, conf=None, eps=1e-7, beta=1.0, select=0):
+    """cmu_hist_curves of histogram rows counts (...,2,NB+1) int64 (+ conf (...,NB+1) uint64): (cum (...,4,NB+1) int64 = tp, fp, fn, tn at
+    j / NB; scores (...,5,NB+1) float64 = F-beta, IoU, precision, recall, specificity; summary (...,6) float64 = AUROC, average
+    precision, ECE, MCE, best j, the selected score there).  ``select``: 0 F-beta, 1 IoU, 2 Youden's J."""
+    if not counts.is_cuda or (conf is not None and not conf.is_cuda):
+        raise RuntimeError("hist_curves runs on the GPU only; there is no CPU fallback in this package")
+    if counts.dtype != torch.int64 or counts.dim() < 2 or counts.shape[-2] != 2 or not counts.is_contiguous() or counts.numel() == 0:
+        raise ValueError(f"hist_curves: counts must be a contiguous (...,2,NB+1) int64 tensor, got {tuple(counts.shape)} {counts.dtype}")
+    bins = check_bins("hist_curves", counts.shape[-1] - 1)
+    lead = tuple(counts.shape[:-2])
+    if conf is not None and (tuple(conf.shape) != lead + (bins + 1,) or conf.dtype not in (torch.uint64, torch.int64) or not conf.is_contiguous()):
+        raise ValueError(f"hist_curves: conf must be a contiguous {lead + (bins + 1,)} uint64 tensor, got {tuple(conf.shape)} {conf.dtype}")
+    if select not in (0, 1, 2) or not eps >= 0 or not beta > 0:
+        raise ValueError(f"hist_curves: select in 0..2, eps >= 0 and beta > 0 (got {select!r}, {eps!r}, {beta!r})")
+    rows = counts.numel() // (2 * (bins + 1))
+    cum = torch.empty(lead + (4, bins + 1), dtype=torch.int64, device=counts.device)
+    scores = torch.empty(lead + (5, bins + 1), dtype=torch.float64, device=counts.device)
+    summary = torch.empty(lead + (6,), dtype=torch.float64, device=counts.device)
+    call("cmu_hist_curves", _p(counts), _p(conf), rows, bins, float(eps), float(beta), int(select), _p(cum), _p(scores), _p(summary), _stream())
+    return cum, scores, summary
+
+
+def threshold_mask(prob, threshold, v_pos=1, v_neg=0, out=None):
+    """uint8 mask of prob's shape: ``v_pos`` where prob > threshold, else ``v_neg`` (a NaN: ``v_neg``); prob float32, contiguous."""
+    if not prob.is_cuda:
+        raise RuntimeError("threshold_mask runs on the GPU only; there is no CPU fallback in this package")
+    if prob.dtype != torch.float32 or not prob.is_contiguous() or prob.numel() == 0:
+        raise ValueError(f"threshold_mask: a non-empty contiguous float32 tensor, got {tuple(prob.shape)} {prob.dtype}")
+    if not (0 <= int(v_pos) <= 255 and 0 <= int(v_neg) <= 255):
+        raise ValueError(f"threshold_mask: v_pos and v_neg are bytes, got {v_pos!r}, {v_neg!r}")
+    if out is None:
+        out = torch.empty(prob.shape, dtype=torch.uint8, device=prob.device)
+    elif out.dtype != torch.uint8 or out.shape != prob.shape or not out.is_contiguous() or out.device != prob.device:
+        raise ValueError("threshold_mask: out must be a contiguous uint8 tensor of prob's shape on its device")
+    call("cmu_threshold_mask", _p(prob), float(threshold), int(v_pos), int(v_neg), _p(out), prob.numel(), _stream())
+    return out

@@ -1001,6 +1001,47 @@ int cmu_pre_crop(const void* src, int elem_bytes, void* dst, int B, int H, int W
 /* out (B,HW) uint8 = 1 where any of the M masks (B,M,HW) uint8 is non-zero at the pixel, else 0.                                         */
 int cmu_pre_integrate_masks(const uint8_t* masks, uint8_t* out, int B, int M, int64_t HW, void* stream);
 
+/* ---------------------------------------------------------------------------------------------
+ * Choosing the operating point: probability histograms, threshold sweeps, ROC / PR and calibration (csrc/prob_hist.hip,
+ * csrc/hist_curves.h; no reference counterpart: the reference fixes the threshold at 0.5).  Integers only up to
+ * the scores: no floating-point atomics, the same bits on every call.  No workspace.
+ *
+ * cmu_prob_hist: ONE pass over src (B,K,H,W) fp32, 1 <= K <= CMU_HIST_MAX_K planes, and a target gives, per row (image or pool, plane)
+ *   counts  (Bout,K,2,NB+1) int64    pixels of the row by ground truth (0, 1) and bin;
+ *   conf    (Bout,K,NB+1)   uint64   the sum over the bin of floor(p * 2^32) (fixed point: order-free; feeds the calibration error);
+ *   invalid (Bout,K)        int32    elements whose probability was NaN or outside [0, 1] (clamped as below).
+ * from_logits = 1: src holds logits; p is the fp32 softmax over the K planes that cmu_seg_stats_fwd thresholds (the same bits), or for
+ * K = 1 the sigmoid of cmu_head_predict.  from_logits = 0: src holds probabilities, one plane per row.
+ * target_kind 0 / 1: fp32 / fp64 planes of src's shape, positive iff y > 0.5.  target_kind 2: a (B,H,W) uint8 label map; a pixel of
+ * label c is positive for plane c only (a label >= K for none); with K = 1 the one plane is "foreground": label != 0.
+ * NB: a power of two in 2..CMU_HIST_MAX_BINS.  bin = ceil(p * NB) in fp32 (the product is exact): bin b holds (b-1)/NB < p <= b/NB, bin
+ * 0 holds p == 0, so "p > j/NB" is exactly "bin > j".  NaN and p < 0 count as 0 (-0.0 is 0), p > 1 and +inf as 1, each also in invalid.
+ * pooled = 1: Bout = 1, every image adds into the same rows; else Bout = B <= 65535.  accumulate = 0: the entry zeroes the three outputs
+ * on the stream first; accumulate = 1: it adds to what they hold (a validation set pools without a host sync).
+ * 16-byte src loads (8-byte for K > 4) when H*W % 4 == 0 (% 2) and src and target are aligned (16 bytes; a label map: 4 / 2), one pixel
+ * per lane otherwise -- decided for the whole tensor.  At most 2^32 pixels per workgroup (256 workgroups): CMU_ERR_ARG past that.       */
+#define CMU_HIST_MAX_K 8
+#define CMU_HIST_MAX_BINS 1024
+int cmu_prob_hist(const float* src, int from_logits, const void* target, int target_kind, int64_t* counts, uint64_t* conf, int32_t* invalid,
+                  int B, int K, int H, int W, int NB, int pooled, int accumulate, void* stream);
+/* From rows histogram rows (counts (rows,2,NB+1), conf (rows,NB+1) or NULL), one workgroup per row:
+ *   cum     (rows,4,NB+1) int64   tp, fp, fn, tn at threshold j/NB, j = 0..NB (tp[j] = positives in bins > j): the integers
+ *                                 cmu_seg_stats_fwd counts at that threshold;
+ *   scores  (rows,5,NB+1) fp64    F-beta ((1+b^2) tp + eps) / ((1+b^2) tp + b^2 fn + fp + eps), IoU (tp + eps) / (tp + fp + fn + eps),
+ *                                 precision (tp + eps) / (tp + fp + eps), recall (tp + eps) / (tp + fn + eps), specificity
+ *                                 (tn + eps) / (tn + fp + eps): Finetuning/metrics.py:135-198, each the Python expression's bits;
+ *   summary (rows,6)      fp64    [0] AUROC = sum_b neg_b (pos_{>b} + pos_b / 2) / (P N) (the trapezoid rule over the NB + 2 points; NaN
+ *                                 when P or N is 0); [1] average precision = sum (R_i - R_{i+1}) Prec_i over descending thresholds with
+ *                                 the all-positive point, without eps (NaN when P is 0); [2] ECE = sum_b |pos_b - conf_b / 2^32| / (P + N);
+ *                                 [3] MCE, the largest per-bin gap |pos_b - conf_b / 2^32| / (pos_b + neg_b); (both NaN without conf);
+ *                                 [4] best_j, the first argmax over j = 1..NB-1 of the score select names (0 F-beta, 1 IoU, 2 Youden's
+ *                                 J = recall + specificity - 1 without eps); [5] that score.                                          */
+int cmu_hist_curves(const int64_t* counts, const uint64_t* conf, int rows, int NB, double eps, double beta, int select, int64_t* cum,
+                    double* scores, double* summary, void* stream);
+/* out[i] = prob[i] > threshold ? v_pos : v_neg for n float32 probabilities (NaN: v_neg); v_pos, v_neg in 0..255.  16 elements per lane
+ * when n % 16 == 0 and both pointers are 16-byte aligned, else one.                                                                  */
+int cmu_threshold_mask(const float* prob, float threshold, int v_pos, int v_neg, uint8_t* out, int64_t n, void* stream);
+
 /* Measurement support (bench.py's roofline block; no reference counterpart): the 16-bit MFMA rate this chip SUSTAINS.
  * Every wave of a one-workgroup-per-CU grid issues iters x 8 back-to-back 32x32x16 MFMAs from registers (no LDS, no
  * memory) or -- lds_fed = 1 -- the same MFMAs fed from LDS at the persistent conv kernel's ratio (6 fragment reads of 1 KB
