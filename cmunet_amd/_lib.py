@@ -5,244 +5,69 @@ raises.  ``build()`` compiles it in-tree with hipcc for gfx950 (works without a 
 """
 import ctypes
 import os
+import re
 import subprocess
 
 _HERE = os.path.dirname(os.path.abspath(__file__))
 CSRC = os.path.join(_HERE, "csrc")
 LIB_PATH = os.environ.get("CMU_LIB_PATH") or os.path.join(CSRC, "libcmunet_hip.so")   # CMU_LIB_PATH: diagnostic builds (tools/)
 
-F32, F16, BF16 = 0, 1, 2
-
-_P = ctypes.c_void_p
-_I = ctypes.c_int
-_L = ctypes.c_int64
-_F = ctypes.c_float
-_U64 = ctypes.c_uint64
-_D = ctypes.c_double
-
-# name -> (restype, argtypes); mirrors include/cmunet_hip.h one to one.
-_SIGS = {
-    "cmu_last_error": (ctypes.c_char_p, []),
-    "cmu_last_kernel": (ctypes.c_char_p, []),
-    "cmu_softmax2_threshold": (_I, [_P, _F, _P, _I, _I, _I, _P]),
-    "cmu_conv3x3_c1_wgrad_bn": (_I, [_P, _P, _I, _P, _L, _P, _L, _P, _P, _P, _P, _P, _P, _I, _I, _I, _I, _I, _P, _P]),
-    "cmu_conv3x3_c1_wgrad_bn_w": (_I, [_P, _P, _I, _P, _L, _P, _P, _P, _P, _P, _P, _P, _I, _I, _I, _I, _I, _P, _P]),
-    "cmu_soft_skeleton_ws_bytes": (_L, [_L]),
-    "cmu_soft_skeleton": (_I, [_P, _P, _I, _I, _I, _I, _P, _P]),
-    "cmu_cldice_sums_ws_bytes": (_L, []),
-    "cmu_cldice_sums": (_I, [_P, _P, _P, _P, _L, _P, _P, _P]),
-    "cmu_softmax_planes": (_I, [_P, _P, _I, _I, _I, _F, _P, _P, _I, _I, _I, _I, _P]),
-    "cmu_softmax_planes_bwd": (_I, [_P, _P, _I, _P, _I, _I, _I, _I, _P]),
-    "cmu_soft_skeleton_save_ws_bytes": (_L, [_L, _I]),
-    "cmu_soft_skeleton_save": (_I, [_P, _P, _I, _I, _I, _I, _P, _P]),
-    "cmu_soft_skeleton_bwd_ws_bytes": (_L, [_L]),
-    "cmu_soft_skeleton_bwd": (_I, [_P, _P, _P, _P, _P, _P, _P, _I, _I, _I, _I, _P, _P]),
-    "cmu_argmax2_mask": (_I, [_P, _I, _P, _I, _I, _I, _I, _P]),
-    "cmu_plane_mask": (_I, [_P, _I, _I, _I, _P, _I, _I, _I, _I, _P]),
-    "cmu_contour_points_ws_bytes": (_L, [_I, _I, _I]),
-    "cmu_contour_points": (_I, [_P, _P, _P, _I, _I, _I, _P, _P]),
-    "cmu_lattice_nearest_ws_bytes": (_L, [_I, _I, _I]),
-    "cmu_lattice_nearest": (_I, [_P, _P, _I, _P, _I, _I, _I, _P, _P]),
-    "cmu_skeletonize": (_I, [_P, _P, _I, _I, _I, _P]),
-    "cmu_hausdorff_finish": (_I, [_P, _P, _P, _P, _P, _P, _I, _P]),
-    "cmu_radius_finish": (_I, [_P, _P, _P, _I, _P]),
-    "cmu_sgd_step": (_I, [_P, _P, _P, _P, _L, _F, _F, _F, _F, _I, _L, _F, _P]),
-    "cmu_sgd_step_amp": (_I, [_P, _P, _P, _P, _L, _F, _F, _F, _F, _I, _L, _F, _P, _P]),
-    "cmu_lamb_block_elems": (_I, []),
-    "cmu_lamb_ws_bytes": (_L, [_I, _I]),
-    "cmu_resize_bicubic_ws_bytes": (_L, [_I, _I, _I, _I, _I]),
-    "cmu_resize_bicubic": (_I, [_P, _I, _I, _I, _P, _P, _P, _I, _I, _P, _P]),
-    "cmu_resize_bicubic_u8_ws_bytes": (_L, [_I, _I, _I, _I, _I]),
-    "cmu_resize_bicubic_u8": (_I, [_P, _I, _I, _I, _P, _P, _P, _I, _I, _P, _P]),
-    "cmu_resize_nearest_u8_ws_bytes": (_L, [_I, _I]),
-    "cmu_resize_nearest_u8": (_I, [_P, _I, _I, _I, _P, _I, _I, _P, _P]),
-    "cmu_two_view": (_I, [_P, _I, _I, _P, _P, _U64, _P, _P, _I, _P]),
-    "cmu_philox_normal": (_I, [_P, _L, _U64, _U64, _P]),
-    "cmu_random_patch_mask": (_I, [_P, _I, _I, _I, _I, _I, _U64, _U64, _P]),
-    "cmu_skinny_gemm_ws_bytes": (_L, [_I, _I, _L]),
-    "cmu_skinny_gemm_fwd": (_I, [_P, _P, _P, _P, _I, _I, _L, _P, _P]),
-    "cmu_skinny_gemm_bwd_ws_bytes": (_L, [_I, _I]),
-    "cmu_skinny_gemm_dgrad": (_I, [_P, _P, _P, _I, _I, _L, _P, _P]),
-    "cmu_skinny_gemm_wgrad": (_I, [_P, _P, _P, _P, _I, _I, _L, _P]),
-    "cmu_lamb_step": (_I, [_P, _P, _P, _P, _P, _P, _P, _P, _I, _P, _P, _I, _F, _F, _F, _F, _I, _I, _F, _I, _I, _L, _F, _P, _P]),
-    "cmu_pack_desc_bytes": (_I, []),
-    "cmu_pack_desc_blocks": (_L, [_I, _I, _I, _I, _I]),
-    "cmu_pack_batch": (_I, [_P, _I, _L, _I, _P]),
-    "cmu_version": (_I, []),
-    "cmu_set_dispatch_override": (_I, [ctypes.c_char_p, _I]),
-    "cmu_dispatch_knob_name": (ctypes.c_char_p, [_I]),
-    "cmu_get_dispatch_knob": (_I, [ctypes.c_char_p, ctypes.POINTER(_I), ctypes.POINTER(_I)]),
-    "cmu_mfma_sustained_rate": (_I, [_I, _I, _I, _I, _P, _P, _P, _P]),
-    "cmu_probe_stream_reduce": (_I, [_P, _P, _P, _L, _I, _I, _P]),
-    "cmu_dtype_size": (_I, [_I]),
-    "cmu_pack_conv3x3_elems": (_L, [_I, _I, _I, _I]),
-    "cmu_pack_conv3x3": (_I, [_P, _P, _I, _I, _I, _I, _P]),
-    "cmu_pack_convT2x2_elems": (_L, [_I, _I, _I, _I]),
-    "cmu_pack_convT2x2": (_I, [_P, _P, _I, _I, _I, _I, _P]),
-    "cmu_conv3x3_c1_fwd": (_I, [_P, _P, _I, _P, _P, _L, _P, _I, _I, _I, _I, _I, _P]),
-    "cmu_conv3x3_fwd": (_I, [_P, _L, _P, _P, _I, _P, _P, _L, _P, _I, _I, _I, _I, _I, _I, _P]),
-    "cmu_conv_ntiles": (_I, [_I, _I, _I]),
-    "cmu_bn_finalize_ws_bytes": (_L, [_I]),
-    "cmu_bn_finalize": (_I, [_P, _I, _L, _P, _P, _P, _P, _P, _F, _F, _I, _P, _P, _P, _P, _I, _P, _P]),
-    "cmu_bnrelu_maxpool_fwd": (_I, [_P, _L, _P, _P, _P, _L, _I, _I, _I, _I, _I, _P]),
-    "cmu_convT2x2_fwd": (_I, [_P, _L, _P, _P, _I, _P, _P, _P, _L, _I, _I, _I, _I, _I, _I, _P]),
-    "cmu_conv1x1_head_fwd": (_I, [_P, _L, _P, _P, _P, _P, _P, _I, _I, _I, _I, _I, _I, _P]),
-    "cmu_head_predict": (_I, [_P, _L, _P, _P, _P, _P, _F, _P, _P, _P, _I, _I, _I, _I, _I, _I, _I, _P]),
-    "cmu_extract_tiles": (_I, [_P, _I, _I, _I, _I, _P, _I, _P, _I, _P, _I, _I, _I, _I, _P, _P]),
-    "cmu_head_probs": (_I, [_P, _L, _P, _P, _P, _P, _P, _I, _P, _I, _I, _I, _I, _I, _I, _P]),
-    "cmu_blend_tiles": (_I, [_P, _I, _I, _I, _P, _I, _P, _I, _I, _I, _I, _I, _P, _P, _F, _P, _P, _P, _I, _P]),
-    "cmu_apply_to_nchw": (_I, [_P, _L, _P, _P, _I, _P, _I, _I, _I, _I, _I, _P]),
-    "cmu_nchw_to_nhwc": (_I, [_P, _P, _L, _I, _I, _I, _I, _I, _P]),
-    "cmu_nhwc_to_nchw": (_I, [_P, _L, _P, _I, _I, _I, _I, _I, _P]),
-    "cmu_bn_bwd_ws_bytes": (_L, [_I]),
-    "cmu_bn_bwd_reduce": (_I, [_P, _L, _P, _L, _P, _P, _P, _P, _P, _P, _P, _I, _I, _I, _I, _I, _P, _P]),
-    "cmu_bn_bwd_apply": (_I, [_P, _L, _P, _L, _P, _P, _P, _P, _P, _P, _L, _I, _I, _I, _I, _I, _P]),
-    "cmu_conv3x3_wgrad_ws_bytes": (_L, [_I, _I, _I, _I, _I, _I]),
-    "cmu_conv3x3_wgrad": (_I, [_P, _L, _P, _P, _I, _P, _L, _P, _I, _I, _I, _I, _I, _I, _P, _P]),
-    "cmu_conv3x3_c1_wgrad_ws_bytes": (_L, [_I, _I, _I, _I]),
-    "cmu_conv3x3_c1_wgrad": (_I, [_P, _P, _I, _P, _L, _P, _I, _I, _I, _I, _I, _P, _P]),
-    "cmu_maxpool_bwd": (_I, [_P, _L, _P, _L, _P, _L, _P, _P, _P, _L, _P, _P, _P, _I, _I, _I, _I, _I, _P]),
-    "cmu_maxpool_bwd2": (_I, [_P, _L, _P, _L, _P, _L, _P, _L, _P, _P, _P, _L, _P, _P, _P, _I, _I, _I, _I, _I, _P]),
-    "cmu_maxpool_bwd_apply": (_I, [_P, _L, _P, _L, _P, _L, _P, _L, _P, _P, _P, _P, _P, _P, _L, _I, _I, _I, _I, _I, _P]),
-    "cmu_bnrelu_maxpool_fwd_masked": (_I, [_P, _L, _P, _P, _P, _I, _P, _L, _I, _I, _I, _I, _I, _P]),
-    "cmu_maxpool_bwd_masked": (_I, [_P, _L, _P, _L, _P, _L, _P, _P, _P, _I, _P, _L, _I, _I, _I, _I, _I, _P]),
-    "cmu_bn_bwd_finalize": (_I, [_P, _L, _P, _P, _P, _I, _P]),
-    "cmu_convT2x2_dgrad": (_I, [_P, _L, _P, _P, _L, _I, _I, _I, _I, _I, _I, _P]),
-    "cmu_convT2x2_dgrad_bn": (_I, [_P, _L, _P, _P, _L, _P, _L, _P, _P, _P, _P, _P, _I, _I, _I, _I, _I, _I, _P]),
-    "cmu_conv3x3_dgrad_bn": (_I, [_P, _L, _P, _P, _L, _P, _L, _P, _P, _P, _P, _P, _I, _I, _I, _I, _I, _I, _P]),
-    "cmu_bn_bwd_finalize_tiles": (_I, [_P, _I, _L, _P, _P, _P, _I, _P, _P]),
-    "cmu_convT2x2_wgrad_ws_bytes": (_L, [_I, _I, _I, _I, _I, _I]),
-    "cmu_convT2x2_wgrad": (_I, [_P, _L, _P, _P, _I, _P, _L, _P, _P, _I, _I, _I, _I, _I, _I, _P, _P]),
-    "cmu_conv1x1_head_bwd_ws_bytes": (_L, [_I, _I, _I, _I, _I]),
-    "cmu_conv1x1_head_bn_apply": (_I, [_P, _P, _L, _P, _P, _P, _P, _P, _P, _P, _L, _I, _I, _I, _I, _I, _I, _P]),
-    "cmu_conv1x1_head_bwd": (_I, [_P, _P, _L, _P, _P, _P, _P, _L, _P, _P, _P, _P, _P, _I, _I, _I, _I, _I, _I, _P, _P]),
-    "cmu_masked_mse_ws_bytes": (_L, [_I, _I]),
-    "cmu_masked_mse_fwd_bwd": (_I, [_P, _I, _I, _P, _P, _P, _P, _F, _P, _I, _I, _I, _P, _P]),
-    "cmu_softmax_ce_dice_ws_bytes": (_L, [_I, _I, _I]),
-    "cmu_softmax_ce_dice_fwd_bwd": (_I, [_P, _P, _P, _P, _F, _I, _I, _I, _P, _P]),
-    "cmu_seg_stats_ws_bytes": (_L, [_I]),
-    "cmu_seg_stats_fwd": (_I, [_P, _P, _I, _P, _F, _P, _I, _I, _I, _I, _P, _P]),
-    "cmu_seg_stats_bwd": (_I, [_P, _P, _I, _P, _P, _P, _P, _P, _I, _I, _I, _I, _P]),
-    "cmu_pointwise_loss_ws_bytes": (_L, []),
-    "cmu_pointwise_loss_fwd": (_I, [_I, _P, _P, _I, _P, _P, _P, _L, _I, _L, _P, _P]),
-    "cmu_pointwise_loss_bwd": (_I, [_I, _P, _P, _I, _P, _P, _P, _P, _L, _I, _L, _P]),
-    "cmu_index_ce_ws_bytes": (_L, []),
-    "cmu_index_ce_fwd": (_I, [_P, _P, _I, _I, _I, _P, _L, _P, _I, _I, _I, _I, _P, _P]),
-    "cmu_index_ce_bwd": (_I, [_P, _P, _I, _I, _I, _P, _L, _P, _P, _I, _I, _I, _I, _P]),
-    "cmu_infonce_inbatch_fwd_bwd": (_I, [_P, _P, _P, _P, _I, _I, _I, _I, _F, _F, _P]),
-    "cmu_moco_ws_bytes": (_L, [_I, _I, _I]),
-    "cmu_moco_infonce_enqueue": (_I, [_P, _P, _P, _I, _P, _P, _P, _P, _P, _I, _I, _I, _F, _P, _P]),
-    "cmu_l2_normalize_rows": (_I, [_P, _P, _I, _I, _P]),
-    "cmu_l2_normalize_rows_bwd": (_I, [_P, _P, _P, _I, _I, _P]),
-    "cmu_moco_logits_assemble": (_I, [_P, _P, _P, _P, _I, _I, _I, _F, _P]),
-    "cmu_moco_logits_split": (_I, [_P, _P, _I, _I, _F, _P]),
-    "cmu_moco_logits_addpos": (_I, [_P, _P, _P, _I, _I, _I, _F, _P]),
-    "cmu_row_cross_entropy": (_I, [_P, _P, _P, _P, _P, _P, _I, _I, _P]),
-    "cmu_scale_by_device_scalar": (_I, [_P, _P, _L, _P]),
-    "cmu_patchify": (_I, [_P, _P, _I, _I, _I, _I, _I, _I, _P]),
-    "cmu_masked_stats_rows": (_I, []),
-    "cmu_masked_channel_stats": (_I, [_P, _L, _P, _I, _I, _P, _I, _I, _I, _I, _I, _P]),
-    "cmu_mask_select": (_I, [_P, _L, _P, _P, _I, _P, _I, _I, _P, _P, _L, _I, _I, _I, _I, _I, _P]),
-    "cmu_bn_bwd_reduce_masked": (_I, [_P, _L, _P, _L, _P, _P, _P, _P, _P, _P, _P, _P, _I, _L, _I, _I, _I, _I, _I, _P, _P]),
-    "cmu_bn_bwd_apply_masked": (_I, [_P, _L, _P, _L, _P, _P, _P, _P, _P, _P, _L, _P, _I, _I, _I, _I, _I, _I, _P]),
-    "cmu_sparse_tile_list": (_I, [_P, _I, _I, _I, _I, _I, _I, _P, _P, _P]),
-    "cmu_conv3x3_tiles_supported": (_I, [_I, _I, _I, _I, _I, _I]),
-    "cmu_rows_channel_stats": (_I, [_P, _L, _P, _P, _P, _I, _I, _I, _I, _I, _P]),
-    "cmu_bn_bwd_reduce_rows": (_I, [_P, _L, _P, _L, _P, _P, _P, _P, _P, _P, _P, _P, _P, _L, _L, _I, _I, _I, _I, _I, _P, _P]),
-    "cmu_sparse_tile_lists_max": (_I, []),
-    "cmu_sparse_tile_lists": (_I, [_P, _I, _I, _I, _P, _P, _P, _P, _P, _P]),
-    "cmu_sparse_pixel_lists": (_I, [_P, _P, _I, _I, _I, _P, _P, _P, _P, _P]),
-    "cmu_conv3x3_c1_fwd_tiles_rows": (_I, [_L]),
-    "cmu_conv3x3_c1_fwd_tiles": (_I, [_P, _P, _I, _P, _P, _L, _P, _P, _P, _L, _I, _I, _I, _I, _I, _P]),
-    "cmu_conv3x3_c1_wgrad_bn_tiles": (_I, [_P, _P, _I, _P, _L, _P, _L, _P, _P, _P, _P, _P, _P, _P, _P, _L, _P, _I, _I, _I, _I, _I, _P, _P]),
-    "cmu_cells_supported": (_I, [_I, _I, _I, _I, _I, _I]),
-    "cmu_bn_bwd_apply_cells": (_I, [_P, _L, _P, _L, _P, _P, _P, _P, _P, _P, _L, _P, _I, _I, _I, _I, _I, _I, _I, _P]),
-    "cmu_mask_select_cells": (_I, [_P, _L, _P, _P, _I, _P, _I, _I, _P, _P, _L, _I, _I, _I, _I, _I, _P]),
-    "cmu_maxpool_bwd_cells": (_I, [_P, _L, _P, _L, _P, _L, _P, _P, _P, _I, _P, _L, _I, _I, _I, _I, _I, _P]),
-    "cmu_cells_stats_rows": (_I, []),
-    "cmu_cells_channel_stats": (_I, [_P, _L, _P, _I, _P, _I, _I, _I, _I, _I, _P]),
-    "cmu_bn_bwd_reduce_cells": (_I, [_P, _L, _P, _L, _P, _P, _P, _P, _P, _P, _P, _P, _I, _L, _I, _I, _I, _I, _I, _P, _P]),
-    "cmu_cells_channel_sum_ws_bytes": (_L, [_I]),
-    "cmu_cells_channel_sum": (_I, [_P, _L, _P, _I, _I, _P, _P, _I, _I, _I, _I, _I, _P]),
-    "cmu_sparse_pixel_list_ws_bytes": (_L, [_I, _I]),
-    "cmu_sparse_pixel_list": (_I, [_P, _I, _I, _I, _I, _P, _L, _P, _P, _P]),
-    "cmu_conv3x3_rows_supported": (_I, [_I, _I, _I, _I, _I, _I]),
-    "cmu_conv3x3_fwd_rows": (_I, [_P, _L, _P, _P, _L, _P, _P, _L, _I, _I, _I, _I, _I, _I, _P]),
-    "cmu_conv3x3_fwd_tiles": (_I, [_P, _L, _P, _P, _I, _P, _P, _L, _P, _P, _I, _I, _I, _I, _I, _I, _P]),
-    "cmu_conv3x3_wgrad_tile_h": (_I, [_I, _I, _I, _I, _I, _I]),
-    "cmu_conv3x3_wgrad_tiles": (_I, [_P, _L, _P, _P, _I, _P, _L, _P, _P, _P, _I, _I, _I, _I, _I, _I, _I, _P, _P]),
-    "cmu_spark_loss_ws_bytes": (_L, [_I, _I]),
-    "cmu_spark_loss_fwd_bwd": (_I, [_P, _P, _P, _P, _P, _F, _I, _I, _I, _P, _P]),
-    "cmu_gap_fwd": (_I, [_P, _L, _P, _P, _P, _I, _I, _I, _I, _I, _P]),
-    "cmu_gap_bwd": (_I, [_P, _P, _L, _I, _I, _I, _I, _I, _P]),
-    "cmu_ema_update": (_I, [_P, _P, _L, _F, _P]),
-    "cmu_adam_step": (_I, [_P, _P, _P, _P, _P, _L, _F, _F, _F, _F, _F, _I, _L, _F, _P, _P]),
-    "cmu_adam_ema_step": (_I, [_P, _P, _P, _P, _P, _L, _F, _F, _F, _F, _F, _I, _L, _F, _P, _I, _P, _P, _P, _F, _P]),
-    "cmu_skinny16_gemm_ws_bytes": (_L, [_I, _I, _L]),
-    "cmu_skinny16_gemm_fwd": (_I, [_P, _P, _P, _P, _I, _I, _L, _I, _P, _P]),
-    "cmu_skinny16_gemm_dgrad": (_I, [_P, _P, _P, _I, _I, _L, _I, _P]),
-    "cmu_skinny16_gemm_wgrad": (_I, [_P, _P, _P, _P, _I, _I, _L, _I, _P]),
-    "cmu_bn1d_colsums": (_I, [_P, _P, _I, _I, _P]),
-    "cmu_bn1d_relu_fwd": (_I, [_P, _P, _L, _P, _P, _P, _P, _F, _F, _I, _I, _P, _P, _P, _I, _I, _P]),
-    "cmu_bn1d_bwd_colsums": (_I, [_P, _P, _P, _P, _P, _I, _P, _I, _I, _P]),
-    "cmu_bn1d_relu_bwd": (_I, [_P, _P, _P, _P, _P, _P, _I, _P, _L, _P, _P, _P, _I, _I, _P]),
-    "cmu_conv1x1_nchw_fwd": (_I, [_P, _L, _P, _P, _I, _P, _P, _P, _I, _I, _I, _I, _I, _I, _P]),
-    "cmu_genesis_rec_bytes": (_I, []),
-    "cmu_genesis_segments": (_I, [_I, _I]),
-    "cmu_genesis_sample": (_I, [_P, _P, _P, _I, _I, _I, _I, _I, _D, _D, _D, _D, _D, _U64, _U64, _P]),
-    "cmu_genesis_gather_shuffle": (_I, [_P, _P, _P, _P, _P, _P, _P, _I, _I, _I, _P]),
-    "cmu_genesis_bezier_ws_bytes": (_L, [_I]),
-    "cmu_genesis_bezier": (_I, [_P, _P, _I, _I, _I, _P, _P, _P]),
-    "cmu_genesis_intensity_paint": (_I, [_P, _P, _P, _U64, _U64, _P, _I, _I, _I, _P]),
-    "cmu_genesis_mae": (_I, [_P, _P, _P, _P, _P, _I, _I, _I, _P]),
-    "cmu_ftaug_rec_layout": (_I, [_P, _I]),
-    "cmu_ftaug_max_ksize": (_I, []),
-    "cmu_ftaug_sample": (_I, [_P, _I, _I, _I, _I, _P, _I, _U64, _U64, _P]),
-    "cmu_ftaug_photometric": (_I, [_P, _I, _I, _I, _P, _P, _U64, _U64, _I, _P, _I, _P]),
-    "cmu_ftaug_apply": (_I, [_P, _P, _I, _I, _I, _P, _P, _U64, _U64, _I, _P, _P, _I, _P]),
-    "cmu_ftaug_resize_ws_bytes": (_L, [_I, _I, _I]),
-    "cmu_ftaug_resize_onehot": (_I, [_P, _P, _I, _I, _I, _P, _P, _U64, _U64, _I, _P, _I, _P, _P, _I, _I, _P, _P]),
-    "cmu_mocoviews_rec_layout": (_I, [_P, _I]),
-    "cmu_mocoviews_max_ksize": (_I, []),
-    "cmu_mocoviews_sample": (_I, [_P, _I, _I, _I, _P, _I, _U64, _U64, _P]),
-    "cmu_mocoviews_geometry": (_I, [_P, _I, _I, _I, _P, _I, _I, _I, _P, _I, _P, _P]),
-    "cmu_mocoviews_max": (_I, [_P, _P, _I, _P]),
-    "cmu_mocoviews_noise": (_I, [_P, _I, _I, _P, _P, _P, _U64, _U64, _P]),
-    "cmu_mse_ws_bytes": (_L, []),
-    "cmu_mse_fwd_bwd": (_I, [_P, _I, _P, _P, _P, _F, _P, _I, _I, _I, _P, _P]),
-    "cmu_label_components_ws_bytes": (_L, [_I, _I, _I]),
-    "cmu_label_components": (_I, [_P, _I, _I, _P, _P, _I, _I, _I, _P, _P]),
-    "cmu_component_sizes": (_I, [_P, _P, _I, _I, _I, _P]),
-    "cmu_select_largest": (_I, [_P, _I, _P, _I, _I, _I, _P]),
-    "cmu_border_components": (_I, [_P, _P, _I, _I, _I, _P]),
-    "cmu_filter_components": (_I, [_P, _I, _P, _P, _I, _P, _I, _I, _P, _P, _P, _I, _P, _I, _I, _I, _P]),
-    "cmu_edt_columns": (_I, [_P, _I, _I, _P, _I, _I, _I, _P]),
-    "cmu_edt_rows": (_I, [_P, _P, _P, _P, _P, _I, _I, _I, _I, _I, _I, _I, _P]),
-    "cmu_surface_border": (_I, [_P, _I, _P, _I, _I, _I, _P]),
-    "cmu_surface_reduce": (_I, [_P, _I, _P, _I, _P, _P, _P, _I, _I, _I, _P]),
-    "cmu_surface_select": (_I, [_P, _P, _P, _I, _P, _P, _I, _I, _I, _P]),
-    "cmu_pre_stats": (_I, [_P, _I, _P, _I, _I, _I, _P]),
-    "cmu_pre_standardize": (_I, [_P, _I, _P, _P, _I, _I, _I, _P]),
-    "cmu_pre_minmax": (_I, [_P, _I, _P, _P, _I, _I, _I, _P]),
-    "cmu_pre_row_normalize": (_I, [_P, _I, _P, _I, _I, _I, _P]),
-    "cmu_pre_blur_rows": (_I, [_P, _I, _F, _P, _I, _P, _I, _I, _I, _P]),
-    "cmu_pre_unsharp_cols": (_I, [_P, _I, _F, _P, _P, _I, _F, _I, _P, _P, _I, _I, _I, _P]),
-    "cmu_pre_crop": (_I, [_P, _I, _P, _I, _I, _I, _I, _I, _I, _I, _P]),
-    "cmu_pre_integrate_masks": (_I, [_P, _P, _I, _I, _L, _P]),
-    "cmu_prob_hist": (_I, [_P, _I, _P, _I, _P, _P, _P, _I, _I, _I, _I, _I, _I, _I, _P]),
-    "cmu_hist_curves": (_I, [_P, _P, _I, _I, _D, _D, _I, _P, _P, _P, _P]),
-    "cmu_threshold_mask": (_I, [_P, _F, _I, _I, _P, _L, _P]),
-    "cmu_amp_state_bytes": (_I, []),
-    "cmu_amp_init": (_I, [_P, _F, _P]),
-    "cmu_amp_check_finite": (_I, [_P, _L, _P, _P]),
-    "cmu_amp_update": (_I, [_P, _F, _F, _I, _P]),
-}
-
-EXPORTS = tuple(_SIGS.keys())
-
 
 class CmuError(RuntimeError):
     pass
+
+
+_SCALAR = {"int": ctypes.c_int, "int64_t": ctypes.c_int64, "uint64_t": ctypes.c_uint64, "float": ctypes.c_float,
+           "double": ctypes.c_double}
+_RETURN = {"int": ctypes.c_int, "int64_t": ctypes.c_int64, "const char *": ctypes.c_char_p}
+
+
+def _ctype(decl, name):
+    """The ctypes type of one parameter declaration (``const float* const* ptrs`` -> c_void_p); its name and ``const`` are dropped."""
+    tok = decl.replace("*", " * ").split()
+    if len(tok) > 1 and re.fullmatch(r"[A-Za-z_]\w*", tok[-1]) and tok[-1] not in _SCALAR:
+        tok.pop()                       # the parameter's name
+    if "*" in tok:
+        return ctypes.c_char_p if tok == ["const", "char", "*"] else ctypes.c_void_p
+    t = " ".join(w for w in tok if w != "const")
+    if t not in _SCALAR:
+        raise CmuError(f"{name}: no ctypes mapping for the parameter {decl.strip()!r}")
+    return _SCALAR[t]
+
+
+def _parse_header(text):
+    """``(sigs, consts)`` of a C header: ``sigs`` maps every ``cmu_*`` prototype to ``(restype, [argtypes])``, ``consts`` holds the
+    integer ``#define CMU_*`` values and the enumerators.  A prototype whose types are not in the maps above, or a ``cmu_*(`` that is
+    not a prototype this parser understands, raises: a function skipped in silence would be called unbound or untyped."""
+    text = re.sub(r"/\*.*?\*/", " ", text, flags=re.S)
+    text = re.sub(r"//[^\n]*", "", text)
+    declared = set(re.findall(r"\b(cmu_\w+)\s*\(", text))
+    consts = {n: int(v) for n, v in re.findall(r"^[ \t]*#[ \t]*define[ \t]+(CMU_\w+)[ \t]+\(?(-?\d+)\)?[ \t]*$", text, flags=re.M)}
+    for body in re.findall(r"\benum\b[^{;]*\{([^}]*)\}", text):
+        consts.update((n, int(v)) for n, v in re.findall(r"(\w+)\s*=\s*(-?\d+)", body))
+    text = re.sub(r"^[ \t]*#[^\n]*", "", text, flags=re.M)
+    sigs = {}
+    for stmt in text.split(";"):
+        m = re.search(r"\b(cmu_\w+)\s*\(([^()]*)\)\s*$", stmt)
+        if m is None:
+            continue
+        name, params = m.group(1), m.group(2).strip()
+        ret = " ".join(re.split(r"[{}]", stmt[:m.start()])[-1].replace("*", " * ").split())
+        if ret not in _RETURN:
+            raise CmuError(f"{name}: no ctypes mapping for the return type {ret!r}")
+        sigs[name] = (_RETURN[ret], [] if params in ("", "void") else [_ctype(p, name) for p in params.split(",")])
+    if declared != set(sigs):
+        raise CmuError(f"not parsed as prototypes: {sorted(declared ^ set(sigs))}")
+    return sigs, consts
+
+
+# name -> (restype, argtypes) and the CMU_* constants, read from include/cmunet_hip.h (the header csrc/common.h includes): a new
+# entry point needs its prototype there, its definition in csrc/ and its wrapper in ops.py, and nothing here.
+with open(os.path.join(_HERE, os.pardir, "include", "cmunet_hip.h")) as _f:
+    _SIGS, CONST = _parse_header(_f.read())
+
+EXPORTS = tuple(_SIGS.keys())
+F32, F16, BF16 = CONST["CMU_F32"], CONST["CMU_F16"], CONST["CMU_BF16"]
 
 
 def build(verbose=False):

@@ -26,7 +26,7 @@ import torch
 import torch.distributed as dist
 import torch.nn as nn
 
-from . import _lib, ops
+from . import ops
 from .model import DoubleConv, DownBlock, UpBlock, _EngineOwner, _named_state, _param_args, _require_cuda
 from .ops import Act
 from .optim import claim_grad_sink, dp_exchanges
@@ -60,7 +60,7 @@ class _MaskedMSEFn(torch.autograd.Function):
         B, K, H, W = logits.shape
         loss = torch.empty(1, dtype=torch.float32, device=logits.device)
         dl = torch.empty_like(logits)
-        ws = torch.empty(_lib.lib().cmu_masked_mse_ws_bytes(B, H), dtype=torch.uint8, device=logits.device)
+        ws = ops.workspace("cmu_masked_mse_ws_bytes", logits.device, B, H)
         ops.masked_mse_fwd_bwd(logits.detach().contiguous(), channel, img.contiguous(), mask.contiguous(), loss, dl, 1.0, ws)
         ctx.save_for_backward(dl)
         return loss[0]

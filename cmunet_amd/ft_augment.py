@@ -199,7 +199,7 @@ class DeviceTrainingAugmentation:
             n = len(self.class_values)
             img = torch.empty(B, self.size, self.size, dtype=torch.float32, device=dev)
             onehot = torch.empty(B, n, self.size, self.size, dtype=torch.float64, device=dev)
-            ws = torch.empty(_lib.lib().cmu_ftaug_resize_ws_bytes(B, S, self.size), dtype=torch.uint8, device=dev)
+            ws = ops.workspace("cmu_ftaug_resize_ws_bytes", dev, B, S, self.size)
             call("cmu_ftaug_resize_onehot", ops._p(P), ops._p(masks), B, H, W, ops._p(recs), ops._p(noise), self.seed, self.last_offset,
                  int(bool(self.config.clip_float)), self._cls, n, ops._p(img), ops._p(onehot), S, self.size, ops._p(ws), ops._stream())
         return img, onehot

@@ -197,7 +197,7 @@ class GenesisPairGenerator:
             self.blocks = torch.zeros(B * NBLOCKS * 4, dtype=torch.int16, device=dev)
             self.perms = torch.zeros(B * NBLOCKS * self.slot, dtype=torch.uint8, device=dev)
             self.minmax = torch.zeros(B * l.cmu_genesis_segments(H, W) * 2, dtype=torch.float32, device=dev)
-            self.ws = torch.empty(l.cmu_genesis_bezier_ws_bytes(B), dtype=torch.uint8, device=dev)
+            self.ws = ops.workspace("cmu_genesis_bezier_ws_bytes", dev, B)
         self.last_noise = None
 
     def __iter__(self):
@@ -268,7 +268,7 @@ def mse_fwd_bwd(logits, y, loss, dlogits, loss_scale=1.0, amp=None, ws=None):
     B, K, H, W = logits.shape
     assert y.shape == (B, H, W) and y.dtype == torch.float32 and y.is_contiguous() and logits.is_contiguous()
     if ws is None:
-        ws = torch.empty(_lib.lib().cmu_mse_ws_bytes(), dtype=torch.uint8, device=logits.device)
+        ws = ops.workspace("cmu_mse_ws_bytes", logits.device)
     call("cmu_mse_fwd_bwd", ops._p(logits), K, ops._p(y), ops._p(loss), ops._p(dlogits), float(loss_scale),
          ops._p(None if amp is None else amp.state), B, H, W, ops._p(ws), ops._stream())
     return loss
@@ -293,7 +293,7 @@ class GenesisPretrainer(ArenaTrainer):
         self.sd.update(dict(model.named_buffers()))
         self.loss = torch.zeros(1, dtype=torch.float32, device=self.device)
         self.vloss = torch.zeros(1, dtype=torch.float32, device=self.device)
-        self._ws = torch.empty(_lib.lib().cmu_mse_ws_bytes(), dtype=torch.uint8, device=self.device)
+        self._ws = ops.workspace("cmu_mse_ws_bytes", self.device)
         self._dlogits = None
 
     def set_epoch(self, epoch):

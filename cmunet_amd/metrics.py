@@ -136,7 +136,7 @@ class _SegStatsFn(torch.autograd.Function):
         B, K, H, W = logits.shape
         out = torch.empty(6, dtype=torch.float32, device=logits.device)
         dl = torch.empty_like(logits)
-        ws = torch.empty(_lib.lib().cmu_softmax_ce_dice_ws_bytes(B, H, W), dtype=torch.uint8, device=logits.device)
+        ws = ops.workspace("cmu_softmax_ce_dice_ws_bytes", logits.device, B, H, W)
         ops.softmax_ce_dice_fwd_bwd(logits.detach().contiguous(), y1h.contiguous(), out, dl, 1.0, ws)
         ctx.save_for_backward(dl)
         return out
@@ -219,7 +219,7 @@ class _SegTableFn(torch.autograd.Function):
     def forward(ctx, logits, y, class_w, threshold):
         K = logits.shape[1]
         table = torch.empty(1 + 5 * K, dtype=torch.float64, device=logits.device)
-        ws = torch.empty(_lib.lib().cmu_seg_stats_ws_bytes(K), dtype=torch.uint8, device=logits.device)
+        ws = ops.workspace("cmu_seg_stats_ws_bytes", logits.device, K)
         lg = logits.detach().contiguous()
         ops.seg_stats_fwd(lg, y, class_w, threshold, table, ws)
         ctx.save_for_backward(lg, y, class_w)
@@ -411,7 +411,7 @@ def _cldice_planes_sums(logits, y, keep, threshold, num_iter, save):
     yt = torch.empty_like(yp)
     ops.softmax_planes(logits, y, keep, threshold, yp, yt)
     sp, st = torch.empty_like(yp), torch.empty_like(yp)
-    ws = torch.empty(_lib.lib().cmu_soft_skeleton_ws_bytes(yp.numel()), dtype=torch.uint8, device=dev)
+    ws = ops.workspace("cmu_soft_skeleton_ws_bytes", dev, yp.numel())
     kept = ops.soft_skeleton_save(yp, sp, num_iter) if save else ops.soft_skeleton(yp, sp, num_iter, ws)
     ops.soft_skeleton(yt, st, num_iter, ws)
     out4 = torch.empty(4, dtype=torch.float32, device=dev)
@@ -480,7 +480,7 @@ class soft_cldice(Loss):
         yt = y_true[:, 1].detach().float().contiguous()
         yp = torch.empty(B, H, W, dtype=torch.float32, device=y_pred.device)
         ops.softmax2_threshold(logits, self.threshold, yp)
-        ws = torch.empty(_lib.lib().cmu_soft_skeleton_ws_bytes(B * H * W), dtype=torch.uint8, device=y_pred.device)
+        ws = ops.workspace("cmu_soft_skeleton_ws_bytes", y_pred.device, B * H * W)
         sp, st = torch.empty_like(yp), torch.empty_like(yp)
         ops.soft_skeleton(yp, sp, self.num_iter, ws)
         ops.soft_skeleton(yt, st, self.num_iter, ws)
@@ -545,7 +545,7 @@ def _nearest(seeds, queries, query_pixels, H, W):
     if W > 512:
         raise NotImplementedError(f"geometry metrics: W <= 512 (got {W})")
     out = torch.empty(B, 4, dtype=torch.float64, device=seeds.device)
-    ws = torch.empty(_lib.lib().cmu_lattice_nearest_ws_bytes(B, H, W), dtype=torch.uint8, device=seeds.device)
+    ws = ops.workspace("cmu_lattice_nearest_ws_bytes", seeds.device, B, H, W)
     _lib.call("cmu_lattice_nearest", ops._p(seeds), ops._p(queries), int(query_pixels), ops._p(out), B, H, W, ops._p(ws), ops._stream())
     return out
 
@@ -877,7 +877,7 @@ class _PointwiseSumFn(torch.autograd.Function):
     def forward(ctx, x, y, kind, chan_w, chan_pw):
         xc = x.detach().contiguous()
         out = torch.empty(1, dtype=torch.float64, device=x.device)
-        ws = torch.empty(_lib.lib().cmu_pointwise_loss_ws_bytes(), dtype=torch.uint8, device=x.device)
+        ws = ops.workspace("cmu_pointwise_loss_ws_bytes", x.device)
         ops.pointwise_loss_fwd(kind, xc, y, chan_w, chan_pw, out, ws)
         ctx.save_for_backward(xc, y, chan_w, chan_pw)
         ctx.kind = kind
@@ -993,7 +993,7 @@ class _IndexCEFn(torch.autograd.Function):
     def forward(ctx, x, target, onehot, log_input, keep, class_w, ignore_index):
         xc = x.detach().contiguous()
         table = torch.empty(3, dtype=torch.float64, device=x.device)
-        ws = torch.empty(_lib.lib().cmu_index_ce_ws_bytes(), dtype=torch.uint8, device=x.device)
+        ws = ops.workspace("cmu_index_ce_ws_bytes", x.device)
         ops.index_ce_fwd(xc, target, onehot, log_input, keep, class_w, ignore_index, table, ws)
         ctx.save_for_backward(xc, target, class_w)
         ctx.cfg = (onehot, log_input, keep, ignore_index)

@@ -19,7 +19,7 @@ import torch.distributed as dist
 import torch.nn as nn
 import torch.nn.functional as F
 
-from . import _lib, ops
+from . import ops
 from .cmunet import UNet_encoder as _MaskEncoder, concat_all_gather
 from .optim import dp_exchanges
 from .model import _EngineOwner, _named_state, _param_args, _require_cuda
@@ -379,7 +379,7 @@ class _MocoLossFn(torch.autograd.Function):
             keys_all = concat_all_gather(kn)                       # moco2_module.py:163-164
         loss = torch.empty(1, dtype=torch.float32, device=dev)
         dq = torch.empty_like(q_raw)
-        ws = torch.empty(_lib.lib().cmu_moco_ws_bytes(B, D, K), dtype=torch.uint8, device=dev)
+        ws = ops.workspace("cmu_moco_ws_bytes", dev, B, D, K)
         ops.moco_infonce_enqueue(q_raw.detach().contiguous(), k_raw.detach().contiguous(), keys_all, queue, queue_ptr, loss, dq,
                                  None, temperature, ws)
         ctx.save_for_backward(dq)

@@ -12,7 +12,7 @@ import os
 import torch
 
 from . import _lib
-from ._lib import F32, F16, BF16, call
+from ._lib import CONST, F32, F16, BF16, call
 
 TORCH_DT = {F32: torch.float32, F16: torch.float16, BF16: torch.bfloat16}
 DT_OF = {v: k for k, v in TORCH_DT.items()}
@@ -39,6 +39,12 @@ def _p(t):
     assert t.is_cuda, "HIP path: tensor must live on the GPU"
     return _lib.devptr(t.data_ptr(), t.device.index)
 
+
+def workspace(size_fn_name, device, *size_args):
+    """The uint8 workspace of ``size_fn_name(*size_args)`` bytes on ``device`` (``size_fn_name``: one of the ``cmu_*_ws_bytes`` queries)."""
+    if not size_fn_name.endswith("_ws_bytes") or size_fn_name not in _lib._SIGS:
+        raise _lib.CmuError(f"{size_fn_name} is not a workspace size query of the library")
+    return torch.empty(getattr(_lib.lib(), size_fn_name)(*size_args), dtype=torch.uint8, device=device)
 
 
 def mfma_sustained_rate(dt="f16", pattern=0, lds_fed=False, iters=60000, device="cuda"):
@@ -542,8 +548,9 @@ def seg_stats_bwd(logits, y, class_w, g_ce, g_tp, g_spr, dlogits):
          _p(_f32c(dlogits)), B, K, H, W, _stream())
 
 
-PWL_KINDS = {"l1": 0, "mse": 1, "bce": 2, "bce_with_logits": 3}       # CMU_PWL_* of the header
-PWL_MAX_C = 8
+PWL_KINDS = {"l1": CONST["CMU_PWL_L1"], "mse": CONST["CMU_PWL_MSE"], "bce": CONST["CMU_PWL_BCE"],
+             "bce_with_logits": CONST["CMU_PWL_BCE_WITH_LOGITS"]}
+PWL_MAX_C = CONST["CMU_PWL_MAX_C"]
 
 
 def _pwl_args(kind, x, y, chan_w, chan_pw):
@@ -582,8 +589,9 @@ def pointwise_loss_bwd(kind, x, y, chan_w, chan_pw, g, dx):
          outer, C, inner, _stream())
 
 
-ICE_LABEL_KINDS = {torch.int64: 0, torch.int32: 1, torch.uint8: 2, torch.float32: 3, torch.float64: 4}    # CMU_ICE_LABEL_*
-ICE_ONEHOT_KINDS = {torch.float32: 5, torch.float64: 6}                                                      # CMU_ICE_ONEHOT_*
+ICE_LABEL_KINDS = {torch.int64: CONST["CMU_ICE_LABEL_I64"], torch.int32: CONST["CMU_ICE_LABEL_I32"], torch.uint8: CONST["CMU_ICE_LABEL_U8"],
+                   torch.float32: CONST["CMU_ICE_LABEL_F32"], torch.float64: CONST["CMU_ICE_LABEL_F64"]}
+ICE_ONEHOT_KINDS = {torch.float32: CONST["CMU_ICE_ONEHOT_F32"], torch.float64: CONST["CMU_ICE_ONEHOT_F64"]}
 
 
 def _ice_args(x, target, onehot, keep, class_w):
@@ -706,7 +714,7 @@ def soft_skeleton(img, skel, num_iter, ws=None):
     """skel = the soft skeleton of the fp32 (planes, H, W) stack ``img`` after ``num_iter`` rounds (metrics.py:448-490)."""
     P, H, W = img.shape
     if ws is None:
-        ws = torch.empty(_lib.lib().cmu_soft_skeleton_ws_bytes(img.numel()), dtype=torch.uint8, device=img.device)
+        ws = workspace("cmu_soft_skeleton_ws_bytes", img.device, img.numel())
     call("cmu_soft_skeleton", _p(_f32c(img)), _p(_f32c(skel)), P, H, W, int(num_iter), _p(ws), _stream())
 
 
@@ -746,7 +754,7 @@ def soft_skeleton_save(img, skel, num_iter, kept=None):
     """``soft_skeleton`` (the same bits) that keeps its level images and running skeletons for ``soft_skeleton_bwd``; returns them."""
     P, H, W = img.shape
     if kept is None:
-        kept = torch.empty(_lib.lib().cmu_soft_skeleton_save_ws_bytes(img.numel(), int(num_iter)), dtype=torch.uint8, device=img.device)
+        kept = workspace("cmu_soft_skeleton_save_ws_bytes", img.device, img.numel(), int(num_iter))
     assert kept.numel() >= _lib.lib().cmu_soft_skeleton_save_ws_bytes(img.numel(), int(num_iter)) and skel.shape == img.shape
     call("cmu_soft_skeleton_save", _p(_f32c(img)), _p(_f32c(skel)), P, H, W, int(num_iter), _p(kept), _stream())
     return kept
@@ -763,7 +771,7 @@ def soft_skeleton_bwd(img, kept, num_iter, dimg, g_skel=None, g4=None, y_true=No
     if g4 is not None:
         assert g4.dtype == torch.float64 and g4.numel() == 4 and g4.is_contiguous() and y_true is not None and skel_true is not None
     if ws is None:
-        ws = torch.empty(_lib.lib().cmu_soft_skeleton_bwd_ws_bytes(img.numel()), dtype=torch.uint8, device=img.device)
+        ws = workspace("cmu_soft_skeleton_bwd_ws_bytes", img.device, img.numel())
     call("cmu_soft_skeleton_bwd", _p(_f32c(img)), _p(kept), _p(g_skel), _p(g4), _p(y_true), _p(skel_true), _p(_f32c(dimg)), P, H, W,
          int(num_iter), _p(ws), _stream())
 
@@ -771,7 +779,7 @@ def soft_skeleton_bwd(img, kept, num_iter, dimg, g_skel=None, g4=None, y_true=No
 def cldice_sums(skel_pred, y_true, skel_true, y_pred, out4, ws=None):
     """out4 = (sum skel_pred*y_true, sum skel_pred, sum skel_true*y_pred, sum skel_true) over same-sized fp32 tensors."""
     if ws is None:
-        ws = torch.empty(_lib.lib().cmu_cldice_sums_ws_bytes(), dtype=torch.uint8, device=skel_pred.device)
+        ws = workspace("cmu_cldice_sums_ws_bytes", skel_pred.device)
     call("cmu_cldice_sums", _p(_f32c(skel_pred)), _p(_f32c(y_true)), _p(_f32c(skel_true)), _p(_f32c(y_pred)), skel_pred.numel(),
          _p(out4), _p(ws), _stream())
 
@@ -842,7 +850,7 @@ def cells_channel_sum(x, active, out, invert=False, ws=None):
     """out[c] (fp32, C) = sum of x over the pixels of the active / masked (``invert``) patches: the mask-token gradient."""
     assert out.dtype == torch.float32 and out.numel() == x.C and out.is_contiguous()
     if ws is None:
-        ws = torch.empty(_lib.lib().cmu_cells_channel_sum_ws_bytes(x.C), dtype=torch.uint8, device=x.buf.device)
+        ws = workspace("cmu_cells_channel_sum_ws_bytes", x.buf.device, x.C)
     call("cmu_cells_channel_sum", x.ptr(), x.ld, _p(active), active.shape[-1], int(invert), _p(out), _p(ws), x.B, x.H, x.W, x.C, x.dt,
          _stream())
 
@@ -905,7 +913,7 @@ class PixelList:
         self.rows = torch.empty(self.capacity, dtype=torch.int32, device=active.device)
         self.count = torch.empty(1, dtype=torch.int32, device=active.device)
         if not defer:
-            ws = torch.empty(_lib.lib().cmu_sparse_pixel_list_ws_bytes(B, f), dtype=torch.uint8, device=active.device)
+            ws = workspace("cmu_sparse_pixel_list_ws_bytes", active.device, B, f)
             call("cmu_sparse_pixel_list", _p(active), f, B, H, W, _p(self.rows), self.capacity, _p(self.count), _p(ws), _stream())
 
 
@@ -1120,7 +1128,7 @@ def resize_bicubic(src, out_h, out_w, boxes=None, flip=None):
         flip = flip.to(device=src.device, dtype=torch.uint8).contiguous()
     out = torch.empty(B, out_h, out_w, dtype=src.dtype, device=src.device)
     entry = "cmu_resize_bicubic_u8" if u8 else "cmu_resize_bicubic"
-    ws = torch.empty(getattr(_lib.lib(), entry + "_ws_bytes")(B, H, W, out_h, out_w), dtype=torch.uint8, device=src.device)
+    ws = workspace(entry + "_ws_bytes", src.device, B, H, W, out_h, out_w)
     call(entry, _p(src), B, H, W, _p(boxes), _p(flip), _p(out), out_h, out_w, _p(ws), _stream())
     return out
 
@@ -1131,7 +1139,7 @@ def resize_nearest(src, out_h, out_w):
     assert src.dtype == torch.uint8 and src.dim() == 3 and src.is_contiguous()
     B, H, W = src.shape
     out = torch.empty(B, out_h, out_w, dtype=torch.uint8, device=src.device)
-    ws = torch.empty(_lib.lib().cmu_resize_nearest_u8_ws_bytes(out_h, out_w), dtype=torch.uint8, device=src.device)
+    ws = workspace("cmu_resize_nearest_u8_ws_bytes", src.device, out_h, out_w)
     call("cmu_resize_nearest_u8", _p(src), B, H, W, _p(out), out_h, out_w, _p(ws), _stream())
     return out
 
@@ -1187,10 +1195,10 @@ def skinny_gemm_fwd(x, weight, bias=None, compute_dt=None):
     dt16 = _mm16(compute_dt, K, 16)
     b = _p(None if bias is None else _f32c(bias))
     if dt16 is not None:
-        ws = torch.empty(_lib.lib().cmu_skinny16_gemm_ws_bytes(M, N, K), dtype=torch.uint8, device=x.device)
+        ws = workspace("cmu_skinny16_gemm_ws_bytes", x.device, M, N, K)
         call("cmu_skinny16_gemm_fwd", _p(x), _p(weight), b, _p(y), M, N, K, dt16, _p(ws), _stream(), work=2.0 * M * N * K)
     else:
-        ws = torch.empty(_lib.lib().cmu_skinny_gemm_ws_bytes(M, N, K), dtype=torch.uint8, device=x.device)
+        ws = workspace("cmu_skinny_gemm_ws_bytes", x.device, M, N, K)
         call("cmu_skinny_gemm_fwd", _p(x), _p(weight), b, _p(y), M, N, K, _p(ws), _stream(), work=2.0 * M * N * K)
     return y
 
@@ -1204,7 +1212,7 @@ def skinny_gemm_dgrad(dy, weight, compute_dt=None):
     if dt16 is not None:
         call("cmu_skinny16_gemm_dgrad", _p(dy), _p(weight), _p(dx), M, N, K, dt16, _stream(), work=2.0 * M * N * K)
     else:
-        ws = torch.empty(_lib.lib().cmu_skinny_gemm_bwd_ws_bytes(M, N), dtype=torch.uint8, device=dy.device)
+        ws = workspace("cmu_skinny_gemm_bwd_ws_bytes", dy.device, M, N)
         call("cmu_skinny_gemm_dgrad", _p(dy), _p(weight), _p(dx), M, N, K, _p(ws), _stream(), work=2.0 * M * N * K)
     return dx
 
@@ -1305,7 +1313,7 @@ def label_components(src, cls=-1, connectivity=8):
         raise ValueError(f"label_components: cls in 0..255, -1 or -2 - c, got {cls}")
     labels = torch.empty(B, H, W, dtype=torch.int32, device=src.device)
     counts = torch.empty(B, dtype=torch.int32, device=src.device)
-    ws = torch.empty(_lib.lib().cmu_label_components_ws_bytes(B, H, W), dtype=torch.uint8, device=src.device)
+    ws = workspace("cmu_label_components_ws_bytes", src.device, B, H, W)
     call("cmu_label_components", _p(src), int(cls), int(connectivity), _p(labels), _p(counts), B, H, W, _p(ws), _stream())
     return labels, counts
 
@@ -1445,7 +1453,7 @@ def surface_select(masked_a, masked_b, ranks):
 
 
 # ---- image preprocessing (csrc/preprocess.hip) ------------------------------------------------
-PRE_MAX_RADIUS = 16      # CMU_PRE_MAX_RADIUS: the largest Gaussian radius of the unsharp mask (half-width 64)
+PRE_MAX_RADIUS = CONST["CMU_PRE_MAX_RADIUS"]      # the largest Gaussian radius of the unsharp mask (half-width 64)
 
 
 def _pre_check(what, t):
@@ -1541,8 +1549,8 @@ def pre_integrate_masks(masks):
 
 
 # probability histograms, threshold sweeps and calibration (csrc/prob_hist.hip, csrc/hist_curves.h)
-HIST_MAX_K = 8           # CMU_HIST_MAX_K
-HIST_MAX_BINS = 1024     # CMU_HIST_MAX_BINS
+HIST_MAX_K = CONST["CMU_HIST_MAX_K"]
+HIST_MAX_BINS = CONST["CMU_HIST_MAX_BINS"]
 HIST_SELECT = {"dice": 0, "fbeta": 0, "iou": 1, "youden": 2}
 _HIST_TARGET_KINDS = {torch.float32: 0, torch.float64: 1, torch.uint8: 2}
 

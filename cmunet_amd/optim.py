@@ -414,7 +414,7 @@ class FusedLAMB:
                        torch.tensor(tens, dtype=torch.int32, device=dev), torch.tensor(t0, dtype=torch.int32, device=dev),
                        torch.tensor(twd, dtype=torch.float32, device=dev))
         self.m, self.v, self.u = torch.zeros_like(flat.arena), torch.zeros_like(flat.arena), torch.empty_like(flat.arena)
-        self.ws = torch.empty(_lib.lib().cmu_lamb_ws_bytes(len(starts), len(twd)), dtype=torch.uint8, device=dev)
+        self.ws = ops.workspace("cmu_lamb_ws_bytes", dev, len(starts), len(twd))
         self.step_count = 0
 
     def zero_grad(self, set_to_none=True):

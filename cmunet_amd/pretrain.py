@@ -22,7 +22,7 @@ import numpy as np
 import torch
 import torch.distributed as dist
 
-from . import _lib, ops
+from . import ops
 from .optim import FlatParams, FusedAdam, FusedLAMB, FusedSGD, cmunet_paramwise_decay, dp_exchanges, dp_world
 
 
@@ -335,7 +335,7 @@ class MaskedReconPretrainer(_ExchangingTrainer):
         logits, ctx = eng.unet_forward(self.sd, img, True, mask, mask_per_sample=not self.ref_compat)
         if self._dlogits is None or self._dlogits.shape != logits.shape:
             self._dlogits = torch.empty_like(logits)
-            self._ws = torch.empty(_lib.lib().cmu_masked_mse_ws_bytes(B, H), dtype=torch.uint8, device=self.device)
+            self._ws = ops.workspace("cmu_masked_mse_ws_bytes", self.device, B, H)
         ops.masked_mse_fwd_bwd(logits, self.pred_channel, img, mask, self.loss, self._dlogits,
                                self.rc_weight * self.loss_scale, self._ws, self.amp)
         eng.grad_target, eng.grad_prefix = self.flat.grad_views, ""

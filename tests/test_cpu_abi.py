@@ -38,6 +38,100 @@ def test_library_builds_loads_and_exports_header():
     assert l.cmu_conv3x3_wgrad_ws_bytes(32, 512, 512, 64, 64, 2) > 0
 
 
+def test_binding_types_of_a_pinned_sample():
+    """The binding is parsed from the header; these signatures are written out by hand (they are the rows of the table the parser replaced),
+    one for every C type the header uses: an int where the header says int64_t, or a float where it says double, fails here."""
+    import ctypes
+    from cmunet_amd import _lib
+    P, I, L, F, D, U64, S = (ctypes.c_void_p, ctypes.c_int, ctypes.c_int64, ctypes.c_float, ctypes.c_double, ctypes.c_uint64, ctypes.c_char_p)
+    pinned = {
+        "cmu_adam_step": (I, [P, P, P, P, P, L, F, F, F, F, F, I, L, F, P, P]),
+        "cmu_two_view": (I, [P, I, I, P, P, U64, P, P, I, P]),
+        "cmu_philox_normal": (I, [P, L, U64, U64, P]),
+        "cmu_genesis_sample": (I, [P, P, P, I, I, I, I, I, D, D, D, D, D, U64, U64, P]),
+        "cmu_hist_curves": (I, [P, P, I, I, D, D, I, P, P, P, P]),
+        "cmu_pack_batch": (I, [P, I, L, I, P]),
+        "cmu_set_dispatch_override": (I, [S, I]),
+        "cmu_dispatch_knob_name": (S, [I]),
+        "cmu_last_error": (S, []),
+        "cmu_seg_stats_ws_bytes": (L, [I]),
+        "cmu_pointwise_loss_ws_bytes": (L, []),
+        "cmu_lamb_step": (I, [P, P, P, P, P, P, P, P, I, P, P, I, F, F, F, F, I, I, F, I, I, L, F, P, P]),
+    }
+    for name, sig in pinned.items():
+        assert _lib._SIGS[name] == sig, (name, _lib._SIGS[name])
+    assert all(isinstance(a, list) and (r in (I, L, S)) for r, a in _lib._SIGS.values())
+
+
+SYNTHETIC_HEADER = """
+/* a block comment with int cmu_in_comment(size_t n); over
+   two lines */
+#ifndef X_H
+#define X_H
+extern "C" {
+typedef enum { CMU_A = 0, CMU_B = 5 } cmu_kind;
+#define CMU_NEG (-3)     /* trailing comment */
+#define CMU_POS 7        // another
+#define CMU_NOT_INT 1.5
+int cmu_none(void);
+const char* cmu_name();   // int cmu_in_line_comment(unsigned n);
+int64_t cmu_many(const float* const* tables, int16_t *q,
+                 int64_t n, uint64_t seed,
+                 float a, double b, const char* tag, const int flag,
+                 void* stream);
+}
+#endif
+"""
+
+
+def test_header_parser_on_synthetic_text():
+    import ctypes
+    from cmunet_amd import _lib
+    P, I = ctypes.c_void_p, ctypes.c_int
+    sigs, consts = _lib._parse_header(SYNTHETIC_HEADER)
+    assert sigs == {"cmu_none": (I, []), "cmu_name": (ctypes.c_char_p, []),
+                    "cmu_many": (ctypes.c_int64, [P, P, ctypes.c_int64, ctypes.c_uint64, ctypes.c_float, ctypes.c_double, ctypes.c_char_p, I, P])}
+    assert consts == {"CMU_A": 0, "CMU_B": 5, "CMU_NEG": -3, "CMU_POS": 7}
+
+
+@pytest.mark.parametrize("proto", ["int cmu_bad(size_t n);", "int cmu_bad(const float* x, unsigned n);", "int cmu_bad(CmuRec rec);",
+                                   "void cmu_bad(int n);", "double cmu_bad(void);", "unsigned cmu_bad(void);",
+                                   "int cmu_bad(int (*callback)(int));", "static inline int cmu_ok(void) { return cmu_bad(1); }"])
+def test_header_parser_refuses_what_it_cannot_type(proto):
+    """An unknown parameter type, an unlisted return type, and a cmu_ function that is no plain prototype all raise, naming the function."""
+    from cmunet_amd import _lib
+    with pytest.raises(_lib.CmuError, match="cmu_bad"):
+        _lib._parse_header("int cmu_ok_before(int n);\n" + proto + "\nint cmu_ok_after(void);\n")
+
+
+def test_constants_come_from_the_header():
+    from cmunet_amd import _lib, ops
+    h = open(os.path.join(ROOT, "include", "cmunet_hip.h")).read()
+    defines = {n: int(v) for n, v in re.findall(r"^#define (CMU_\w+) \(?(-?\d+)\)?", h, flags=re.M)}
+    assert len(defines) == 21
+    enum = {"CMU_F32": 0, "CMU_F16": 1, "CMU_BF16": 2}
+    assert "typedef enum { CMU_F32 = 0, CMU_F16 = 1, CMU_BF16 = 2 } cmu_dtype;" in h
+    assert _lib.CONST == {**defines, **enum}
+    C = _lib.CONST
+    assert (C["CMU_OK"], C["CMU_ERR_ARG"], C["CMU_ERR_UNSUPPORTED"], C["CMU_ERR_WORKSPACE"], C["CMU_ERR_LAUNCH"]) == (0, -1, -2, -3, -4)
+    assert C["CMU_PWL_MAX_C"] == 8 and C["CMU_HIST_MAX_BINS"] == 1024 and C["CMU_HIST_MAX_K"] == 8 and C["CMU_PRE_MAX_RADIUS"] == 16
+    assert (_lib.F32, _lib.F16, _lib.BF16) == (0, 1, 2)
+    assert ops.PWL_KINDS == {"l1": 0, "mse": 1, "bce": 2, "bce_with_logits": 3} and ops.PWL_MAX_C == 8
+    assert (ops.PRE_MAX_RADIUS, ops.HIST_MAX_K, ops.HIST_MAX_BINS) == (16, 8, 1024)
+
+
+def test_workspace_helper_calls_the_named_size_query():
+    import torch
+    from cmunet_amd import _lib, ops
+    _lib.build()
+    ws = ops.workspace("cmu_seg_stats_ws_bytes", "cpu", 3)
+    assert ws.dtype == torch.uint8 and ws.device.type == "cpu" and ws.shape == (_lib.lib().cmu_seg_stats_ws_bytes(3),) and ws.numel() > 0
+    assert ops.workspace("cmu_soft_skeleton_save_ws_bytes", "cpu", 1000, 3).numel() == _lib.lib().cmu_soft_skeleton_save_ws_bytes(1000, 3)
+    for name in ("cmu_version", "cmu_pack_desc_bytes", "cmu_nothing_ws_bytes", "cmu_seg_stats"):
+        with pytest.raises(_lib.CmuError, match=name):
+            ops.workspace(name, "cpu", 3)
+
+
 def test_product_has_no_cpu_fallback():
     import torch
     from cmunet_amd import model as M
