@@ -33,6 +33,10 @@ on ``cmu_index_ce_fwd`` / ``_bwd`` (2..8 classes), which yield three fp64 sums f
 Choosing the threshold (no reference counterpart): ``prob_histogram`` -- one pass of ``cmu_prob_hist`` -- then
 ``threshold_sweep`` / ``best_threshold`` (``cmu_hist_curves``: every threshold j / bins at once) and the threshold-free ``Metric``s
 ``AUROC``, ``AveragePrecision``, ``CalibrationError``.  New names only: every class above keeps its configuration checks.
+Losses for thin, rare foregrounds (no reference counterpart), 2..8 classes, softmax: ``FocalLoss`` on
+``cmu_focal_fwd`` / ``_bwd`` (label maps or one-hot planes), ``TverskyLoss`` from the pair's counter table (``tversky_from_counters``),
+``BoundaryLoss`` and ``HausdorffDTLoss`` on ``cmu_softmax_map_fwd`` / ``_bwd`` with distance maps from the exact on-device transform
+(``signed_distance_maps``, ``distance_fields``: ``cmu_edt_columns`` / ``cmu_edt_rows`` / ``cmu_distance_field``).
 """
 import collections
 import math
@@ -209,6 +213,13 @@ def iou_from_counters(tp, spr, sgt, eps=1e-7, ignore_channels=None):
     """metrics.py:182-198 from the same counters: (intersection + eps) / (sum gt + sum pr - intersection + eps)."""
     tp, spr, sgt = _kept_sums(ignore_channels, tp, spr, sgt)
     return (tp + eps) / (sgt + spr - tp + eps)
+
+
+def tversky_from_counters(tp, spr, sgt, alpha=0.5, beta=0.5, eps=1e-7, ignore_channels=None):
+    """The Tversky index (Salehi et al.) from the same counters, pooled over the kept channels as ``f_score_from_counters`` pools
+    them: (tp + eps) / (tp + alpha fp + beta fn + eps) with fp = spr - tp, fn = sgt - tp.  alpha = beta = 0.5 is the Dice score."""
+    tp, spr, sgt = _kept_sums(ignore_channels, tp, spr, sgt)
+    return (tp + eps) / (tp + alpha * (spr - tp) + beta * (sgt - tp) + eps)
 
 
 class _SegTableFn(torch.autograd.Function):
@@ -1074,6 +1085,300 @@ class RobustCrossEntropyLoss(Loss):
         if self.reduction == "mean":
             return t[0] / t[1] if e == 0.0 else (1.0 - e) * t[0] / t[1] + (e / K) * t[2] / t[1]
         return t[0] if e == 0.0 else (1.0 - e) * t[0] + (e / K) * t[2]
+
+
+# ---------------------------------------------------------------------------------------------
+# Losses for thin, rare foregrounds (no reference counterpart; csrc/map_loss.hip): focal and Tversky against
+# class imbalance, the boundary and Hausdorff distance-transform losses on distance maps from the exact transform of csrc/edt.hip
+# ---------------------------------------------------------------------------------------------
+class _FocalFn(torch.autograd.Function):
+    """table = [sum alpha_t (1 - p_t)^gamma (-log p_t) | sum alpha_t | pixels not ignored] (3 fp64); the backward kernel takes the
+    incoming gradient of table[0] from the device (the other two do not depend on the input)."""
+
+    @staticmethod
+    def forward(ctx, x, target, onehot, class_w, gamma, ignore_index):
+        xc = x.detach().contiguous()
+        table = torch.empty(3, dtype=torch.float64, device=x.device)
+        ops.focal_fwd(xc, target, onehot, class_w, gamma, ignore_index, table)
+        ctx.save_for_backward(xc, target, class_w)
+        ctx.cfg = (onehot, gamma, ignore_index)
+        return table
+
+    @staticmethod
+    def backward(ctx, g):
+        xc, target, class_w = ctx.saved_tensors
+        onehot, gamma, ignore_index = ctx.cfg
+        dx = torch.empty_like(xc)
+        ops.focal_bwd(xc, target, onehot, class_w, gamma, ignore_index, g[0:1].contiguous(), dx)
+        return dx, None, None, None, None, None
+
+
+class FocalLoss(Loss):
+    """Focal loss (Lin et al., 2017) on logits (B,K,H,W), 2 <= K <= 8: -alpha_t (1 - p_t)^gamma log p_t per pixel, against a label map
+    ((B,H,W) or (B,1,H,W) of int64 / int32 / uint8 / fp32 / fp64, as ``RobustCrossEntropyLoss`` takes it) or one-hot planes of the
+    logits' shape (fp32 / fp64; the arg-max over the channels is the label).  ``alpha``: one weight per class, or None.
+    ``reduction``: 'mean' divides the sum by the number of pixels that are not ``ignore_index`` (the paper's and
+    segmentation_models.pytorch's convention), 'weighted_mean' by the sum of their alpha_t (torch's weighted cross entropy), 'sum' by
+    nothing.  With ``gamma=0`` the values are those of ``RobustCrossEntropyLoss(weight=alpha)``: its 'mean' is 'weighted_mean' here,
+    and without ``alpha`` the two means coincide.  A label outside [0, K) that is not ``ignore_index`` makes the value NaN and gets
+    a zero gradient."""
+
+    def __init__(self, gamma=2.0, alpha=None, ignore_index=-100, reduction="mean", **kwargs):
+        super().__init__(**kwargs)
+        if not 0.0 <= float(gamma) <= 1e6:
+            raise ValueError(f"FocalLoss: gamma must be a number >= 0, got {gamma}")
+        self.register_buffer("alpha", None if alpha is None else torch.as_tensor(alpha, dtype=torch.float32).detach().clone().contiguous())
+        if self.alpha is not None and self.alpha.dim() != 1:
+            raise ValueError("FocalLoss: alpha is a vector of one value per class")
+        if reduction == "none":
+            raise NotImplementedError("FocalLoss: reduction 'mean' / 'weighted_mean' / 'sum' on the HIP path (the kernel returns sums)")
+        if reduction not in ("mean", "weighted_mean", "sum"):
+            raise ValueError(f"FocalLoss: {reduction!r} is not a valid value for reduction")
+        self.gamma, self.ignore_index, self.reduction = float(gamma), int(ignore_index), reduction
+
+    def forward(self, y_pr, y_gt):
+        _check_device("FocalLoss", y_pr, y_gt)
+        _check_index_input("FocalLoss", y_pr)
+        B, K, H, W = y_pr.shape
+        onehot = y_gt.shape == y_pr.shape
+        if not onehot:
+            if y_gt.dim() == 4 and y_gt.shape[1] == 1:
+                y_gt = y_gt[:, 0]
+            if y_gt.shape != (B, H, W):
+                raise NotImplementedError(f"FocalLoss: a label map (B,1,H,W) / (B,H,W) or one-hot planes for input {tuple(y_pr.shape)}, got {tuple(y_gt.shape)}")
+        if self.alpha is not None and self.alpha.shape[0] != K:
+            raise ValueError(f"FocalLoss: {self.alpha.shape[0]} class weights for {K} classes")
+        if self.alpha is not None and self.alpha.device != y_pr.device:
+            self.alpha = self.alpha.to(y_pr.device)
+        y = y_gt.detach()
+        if onehot:
+            y = (y if y.dtype in ops.ICE_ONEHOT_KINDS else y.float()).contiguous()
+        else:
+            y = (y if y.dtype in ops.ICE_LABEL_KINDS else y.long()).contiguous()
+        t = _FocalFn.apply(y_pr.float(), y, onehot, self.alpha, self.gamma, self.ignore_index)
+        return t[0] / t[2] if self.reduction == "mean" else t[0] / t[1] if self.reduction == "weighted_mean" else t[0]
+
+
+class TverskyLoss(Loss):
+    """(1 - TI)^gamma with the Tversky index TI = (tp + eps) / (tp + alpha fp + beta fn + eps) of the softmax probabilities over the
+    kept channels pooled (Salehi et al., 2017; gamma != 1: the focal Tversky loss of Abraham & Khan, 2019).  It reads the pair's
+    counter table (``seg_table``), so ``TverskyLoss() + CrossEntropyLoss()`` costs one pass.  ``threshold=None`` is differentiable;
+    with a threshold the value is detached, as for ``DiceLoss``.  ``alpha = beta = 0.5`` is ``DiceLoss(beta=1)`` up to eps."""
+
+    def __init__(self, alpha=0.5, beta=0.5, gamma=1.0, eps=1e-7, activation="softmax", ignore_channels=None, threshold=None, **kwargs):
+        super().__init__(**kwargs)
+        _check_seg_cfg("TverskyLoss", activation, threshold, ignore_channels, eps)
+        if not (float(alpha) >= 0 and float(beta) >= 0 and float(gamma) > 0):
+            raise ValueError(f"TverskyLoss: alpha, beta >= 0 and gamma > 0 (got alpha={alpha}, beta={beta}, gamma={gamma})")
+        self.alpha, self.beta, self.gamma, self.eps = float(alpha), float(beta), float(gamma), float(eps)
+        self.activation, self.threshold = activation, None if threshold is None else float(threshold)
+        self.ignore_channels = None if ignore_channels is None else list(ignore_channels)
+        self._reference_cfg = False          # a term of the K-class pass: a combined Loss that holds it never takes the two-class kernel
+
+    def forward(self, y_pr, y_gt):
+        tp, spr, sgt = _counters(seg_table(y_pr, y_gt, self.threshold, any_weight=True), self.threshold)
+        v = 1.0 - tversky_from_counters(tp, spr, sgt, self.alpha, self.beta, self.eps, self.ignore_channels)
+        if self.gamma != 1.0:
+            v = v ** self.gamma
+        return v if self.threshold is None else v.detach()
+
+
+def _label_map(what, target, classes):
+    """(uint8 label map (B,H,W), K) of a label map ((B,H,W) / (B,1,H,W), any integer or floating dtype; ``classes`` = K is required) or
+    of one-hot planes (B,K,H,W) of a floating dtype, whose arg-max over the channels is the label, as the index CE takes it."""
+    _check_device(what, target)
+    t = target.detach()
+    if t.dim() == 4 and t.is_floating_point() and t.shape[1] > 1:
+        K = t.shape[1]
+        if classes is not None and int(classes) != K:
+            raise ValueError(f"{what}: classes={classes} against {K} one-hot planes")
+        t = torch.argmax(t, dim=1)
+    else:
+        if t.dim() == 4 and t.shape[1] == 1:
+            t = t[:, 0]
+        if t.dim() != 3 or classes is None:
+            raise ValueError(f"{what}: a label map (B,H,W) / (B,1,H,W) with classes=K, or one-hot planes (B,K,H,W); got {tuple(target.shape)}, classes={classes}")
+        K = int(classes)
+    if not 1 <= K <= 255:
+        raise ValueError(f"{what}: 1 <= classes <= 255, got {K}")
+    return t.to(torch.uint8).contiguous(), K
+
+
+class _D2Scratch:
+    """The int32 scratch of the transforms of one set: g (the column pass), and the squared distances to the set and to its complement."""
+
+    def __init__(self, like):
+        self.g, self.to, self.frm = (torch.empty(like.shape, dtype=torch.int32, device=like.device) for _ in range(3))
+
+    def pair(self, src, cls_to, cls_from):
+        ops.edt_rows(ops.edt_columns(src, cls_to, g=self.g), out=self.to)
+        ops.edt_rows(ops.edt_columns(src, cls_from, g=self.g), out=self.frm)
+        return self.to, self.frm
+
+
+def _signed_maps(lab, K, keep):
+    """(B,K,H,W) fp32: plane c of ``keep`` = the signed distance to the boundary of {lab == c}; the other planes are zero."""
+    out = torch.zeros((lab.shape[0], K) + tuple(lab.shape[1:]), dtype=torch.float32, device=lab.device)
+    s = _D2Scratch(lab)
+    for c in keep:
+        ops.distance_field(*s.pair(lab, c, -2 - c), out, c, "signed")
+    return out
+
+
+def signed_distance_maps(target, classes=None):
+    """(B,K,H,W) fp32 signed distance maps of a target (Kervadec et al.'s ``one_hot2dist``): in plane c, a pixel outside class c
+    holds its Euclidean distance to the class, a pixel inside 1 - its distance to the complement; an image in which the class is
+    empty or full holds zeros.  ``target``: a label map (B,H,W) / (B,1,H,W) with ``classes`` = K, or one-hot planes (B,K,H,W) of a
+    floating dtype (arg-max).  Two exact transforms (``ops.edt_columns`` + ``ops.edt_rows``) and one ``ops.distance_field`` per class;
+    H, W <= 4096.  No gradient.  For a dataset whose targets do not change, compute once and pass as ``BoundaryLoss``'s ``maps``."""
+    lab, K = _label_map("signed_distance_maps", target, classes)
+    return _signed_maps(lab, K, range(K))
+
+
+def _mask_sets(what, mask, classes):
+    """-> (K, sets) with sets(c) = (uint8 map (B,H,W), site rule of class c's set, site rule of its complement): 0/1 uint8 planes
+    (B,K,H,W) -- thresholded probabilities, each plane its own set -- or whatever ``_label_map`` takes."""
+    if mask.dim() == 4 and mask.dtype == torch.uint8 and mask.shape[1] > 1:
+        _check_device(what, mask)
+        return mask.shape[1], lambda c: (mask[:, c].contiguous(), -1, 0)
+    lab, K = _label_map(what, mask, classes)
+    return K, lambda c: (lab, c, -2 - c)
+
+
+def distance_fields(mask_a, mask_b=None, alpha=2.0, classes=None):
+    """(B,K,H,W) fp32: per class the distance to the boundary of its set (to the set outside it, to its complement inside) to the
+    power ``alpha`` -- MONAI's ``HausdorffDTLoss.distance_field`` raised -- of ``mask_a``, plus that of ``mask_b`` when given.  A mask:
+    a label map with ``classes`` = K, one-hot planes of a floating dtype (arg-max), or 0/1 uint8 planes (B,K,H,W) such as thresholded
+    probabilities (each plane its own set).  An image whose set is empty or full adds zeros.  No gradient; H, W <= 4096."""
+    if not 0.0 < float(alpha) <= 16.0:
+        raise ValueError(f"distance_fields: 0 < alpha <= 16, got {alpha!r}")
+    K, sets_a = _mask_sets("distance_fields", mask_a, classes)
+    sets_b = None
+    if mask_b is not None:
+        Kb, sets_b = _mask_sets("distance_fields", mask_b, classes)
+        if Kb != K or mask_b.shape[0] != mask_a.shape[0] or mask_b.shape[-2:] != mask_a.shape[-2:]:
+            raise ValueError(f"distance_fields: masks of {tuple(mask_a.shape)} and {tuple(mask_b.shape)} do not describe the same classes and pixels")
+    B, (H, W) = mask_a.shape[0], mask_a.shape[-2:]
+    out = torch.empty((B, K, H, W), dtype=torch.float32, device=mask_a.device)
+    sa = sb = None
+    for c in range(K):
+        src, cls_to, cls_from = sets_a(c)
+        sa = sa or _D2Scratch(src)
+        pair_b = (None, None)
+        if sets_b is not None:
+            src_b, to_b, from_b = sets_b(c)
+            sb = sb or _D2Scratch(src_b)
+            pair_b = sb.pair(src_b, to_b, from_b)
+        ops.distance_field(*sa.pair(src, cls_to, cls_from), out, c, "unsigned", alpha, *pair_b)
+    return out
+
+
+class _SoftmaxMapFn(torch.autograd.Function):
+    """table (K fp64) = sum Wm_c p_c ('linear') or sum Wm_c (p_c - y_c)^2 ('squared') over the kept classes; the backward kernel takes
+    the K incoming gradients from the device.  Wm and y carry no gradient."""
+
+    @staticmethod
+    def forward(ctx, logits, wmap, y, keep, kind):
+        lg = logits.detach().contiguous()
+        table = torch.empty(lg.shape[1], dtype=torch.float64, device=lg.device)
+        ops.softmax_map_fwd(lg, wmap, y, keep, kind, table)
+        ctx.save_for_backward(lg, wmap, y)
+        ctx.cfg = (keep, kind)
+        return table
+
+    @staticmethod
+    def backward(ctx, g):
+        lg, wmap, y = ctx.saved_tensors
+        dl = torch.empty_like(lg)
+        ops.softmax_map_bwd(lg, wmap, y, ctx.cfg[0], ctx.cfg[1], g.contiguous(), dl)
+        return dl, None, None, None, None
+
+
+def _check_map_loss(what, activation, ignore_channels):
+    if activation not in ("softmax", "softmax2d"):
+        raise NotImplementedError(f"{what}: activation 'softmax' / 'softmax2d' only on the HIP path (got {activation!r})")
+    _kept(ops.SEG_MAX_K, ignore_channels)
+
+
+def _check_map_input(what, y_pr, y_gt):
+    _check_device(what, y_pr, y_gt)
+    _check_index_input(what, y_pr)
+    if y_pr.shape[2] > ops.EDT_MAX_SIDE or y_pr.shape[3] > ops.EDT_MAX_SIDE:
+        raise NotImplementedError(f"{what}: H, W <= {ops.EDT_MAX_SIDE} (the distance transform's limit), got {tuple(y_pr.shape)}")
+
+
+class BoundaryLoss(Loss):
+    """The boundary loss of Kervadec et al. (2019): the mean over B x kept classes x H x W of phi_c p_c, with p the softmax and phi_c
+    the signed distance map of class c of the target (``signed_distance_maps``) -- ``einsum(pc, dc).mean()`` over the kept classes.
+    The value can be NEGATIVE: phi is negative inside the target, and a perfect prediction sums it there.  ``forward(y_pr, y_gt)``
+    builds phi from ``y_gt`` (one-hot planes of the logits' shape, or a label map); ``forward(y_pr, y_gt, maps)`` -- or ``maps=`` at
+    construction -- takes a precomputed (B,K,H,W) fp32 map and does not look at ``y_gt``.  The maps carry no gradient."""
+
+    def __init__(self, activation="softmax", ignore_channels=(0,), maps=None, **kwargs):
+        super().__init__(**kwargs)
+        _check_map_loss("BoundaryLoss", activation, ignore_channels)
+        self.activation, self.maps = activation, maps
+        self.ignore_channels = None if ignore_channels is None else list(ignore_channels)
+
+    def forward(self, y_pr, y_gt=None, maps=None):
+        maps = self.maps if maps is None else maps
+        if y_gt is None and maps is None:
+            raise ValueError("BoundaryLoss: a target or precomputed maps")
+        _check_map_input("BoundaryLoss", y_pr, y_pr if maps is not None else y_gt)
+        B, K, H, W = y_pr.shape
+        keep = _kept(K, self.ignore_channels)
+        if maps is None:
+            lab, _ = _label_map("BoundaryLoss", y_gt, K)
+            if lab.shape != (B, H, W):
+                raise ValueError(f"BoundaryLoss: a target of {tuple(y_gt.shape)} for logits of {tuple(y_pr.shape)}")
+            maps = _signed_maps(lab, K, keep)
+        elif maps.shape != y_pr.shape or maps.dtype != torch.float32 or maps.device != y_pr.device:
+            raise ValueError(f"BoundaryLoss: maps must be a float32 tensor of the logits' shape {tuple(y_pr.shape)} on their device")
+        table = _SoftmaxMapFn.apply(y_pr.float(), maps.detach().contiguous(), None, keep, "linear")
+        return table.sum() / float(B * len(keep) * H * W)
+
+
+class HausdorffDTLoss(Loss):
+    """The Hausdorff distance-transform loss of Karimi & Salcudean (2019) as MONAI's ``HausdorffDTLoss`` states it: per kept class the
+    mean over B x H x W of (p_c - y_c)^2 (f_pred,c^alpha + f_target,c^alpha), averaged over the kept classes.  f is the distance to the
+    boundary of a set (``distance_fields``): the target's class, and the DETACHED softmax probability thresholded at ``threshold``
+    (``cmu_softmax_planes`` -> ``cmu_threshold_mask`` -> the exact transform, every step on the device).  The gradient reaches the
+    logits through (p - y)^2 only.  ``y_gt``: one-hot planes of the logits' shape, fp32 / fp64."""
+
+    def __init__(self, alpha=2.0, activation="softmax", ignore_channels=(0,), threshold=0.5, **kwargs):
+        super().__init__(**kwargs)
+        _check_map_loss("HausdorffDTLoss", activation, ignore_channels)
+        if not 0.0 < float(alpha) <= 16.0:
+            raise ValueError(f"HausdorffDTLoss: 0 < alpha <= 16, got {alpha}")
+        if not 0.0 < float(threshold) < 1.0:
+            raise ValueError(f"HausdorffDTLoss: threshold must be inside (0, 1), got {threshold}")
+        self.alpha, self.threshold, self.activation = float(alpha), float(threshold), activation
+        self.ignore_channels = None if ignore_channels is None else list(ignore_channels)
+
+    def _fields(self, logits, lab, keep):
+        """(B,K,H,W) fp32: f_pred^alpha + f_target^alpha on the kept planes, zero on the others."""
+        B, K, H, W = logits.shape
+        out = torch.zeros((B, K, H, W), dtype=torch.float32, device=logits.device)
+        prob = torch.empty((B, H, W), dtype=torch.float32, device=logits.device)
+        mask = torch.empty((B, H, W), dtype=torch.uint8, device=logits.device)
+        sp, st = _D2Scratch(lab), _D2Scratch(lab)
+        for c in keep:
+            ops.softmax_planes(logits, None, [c], None, prob, None)
+            ops.threshold_mask(prob, self.threshold, out=mask)
+            ops.distance_field(*sp.pair(mask, -1, 0), out, c, "unsigned", self.alpha, *st.pair(lab, c, -2 - c))
+        return out
+
+    def forward(self, y_pr, y_gt):
+        _check_map_input("HausdorffDTLoss", y_pr, y_gt)
+        if y_gt.shape != y_pr.shape:
+            raise NotImplementedError("HausdorffDTLoss: one-hot targets of the prediction's shape")
+        B, K, H, W = y_pr.shape
+        keep = _kept(K, self.ignore_channels)
+        y = _float_target(y_gt)
+        lg = y_pr.float()
+        fields = self._fields(lg.detach().contiguous(), _label_map("HausdorffDTLoss", y, K)[0], keep)
+        table = _SoftmaxMapFn.apply(lg, fields, y, keep, "squared")
+        return table.sum() / float(B * len(keep) * H * W)
 
 
 # ---------------------------------------------------------------------------------------------

@@ -1630,3 +1630,103 @@ def threshold_mask(prob, threshold, v_pos=1, v_neg=0, out=None):
         raise ValueError("threshold_mask: out must be a contiguous uint8 tensor of prob's shape on its device")
     call("cmu_threshold_mask", _p(prob), float(threshold), int(v_pos), int(v_neg), _p(out), prob.numel(), _stream())
     return out
+
+
+# ---- focal cross entropy, map-weighted softmax sums, distance fields (csrc/map_loss.hip) -----
+MAP_KINDS = {"linear": 0, "squared": 1}          # cmu_softmax_map_*: sum Wm p | sum Wm (p - y)^2
+FIELD_MODES = {"signed": 0, "unsigned": 1}       # cmu_distance_field: Kervadec's signed distance | MONAI's field to the power alpha
+MAP_LOSS_MAX_BLOCKS = 1024                       # the grid cap of the passes: ``partials`` holds columns x 1024 doubles
+
+
+def map_loss_partials(columns, device):
+    """The fp64 block-partial tensor of cmu_focal_fwd (3 columns) / cmu_softmax_map_fwd (K columns); needs no initialisation."""
+    return torch.empty(columns * MAP_LOSS_MAX_BLOCKS, dtype=torch.float64, device=device)
+
+
+def _focal_args(x, target, onehot, class_w, gamma):
+    B, K, H, W, kind, _ = _ice_args(x, target, onehot, None, class_w)
+    assert class_w is None or class_w.is_cuda
+    gamma = float(gamma)
+    assert 0.0 <= gamma <= 1e6, gamma
+    return B, K, H, W, kind, gamma
+
+
+def focal_fwd(x, target, onehot, class_w, gamma, ignore_index, table, partials=None):
+    """table (3 fp64) = [sum alpha_t q^gamma (-log p_t) | sum alpha_t | pixels not ignored], q = 1 - p_t, of (B,K,H,W) fp32 logits
+    against a (B,H,W) label plane, or (``onehot``) K planes whose arg-max is the label (cmu_focal_fwd)."""
+    B, K, H, W, kind, gamma = _focal_args(x, target, onehot, class_w, gamma)
+    assert table.dtype == torch.float64 and table.numel() == 3 and table.is_contiguous()
+    if partials is None:
+        partials = map_loss_partials(3, x.device)
+    assert partials.dtype == torch.float64 and partials.numel() >= 3 * MAP_LOSS_MAX_BLOCKS and partials.is_contiguous()
+    call("cmu_focal_fwd", _p(_f32c(x)), _p(target), kind, _p(class_w), gamma, int(ignore_index), _p(table), _p(partials), B, K, H, W,
+         _stream())
+
+
+def focal_bwd(x, target, onehot, class_w, gamma, ignore_index, g, dx):
+    """dx (fp32) from the device-resident fp64 gradient g = d / d table[0]; None = zero."""
+    B, K, H, W, kind, gamma = _focal_args(x, target, onehot, class_w, gamma)
+    assert g is None or (g.dtype == torch.float64 and g.numel() == 1 and g.is_contiguous())
+    assert dx.shape == x.shape
+    call("cmu_focal_bwd", _p(_f32c(x)), _p(target), kind, _p(class_w), gamma, int(ignore_index), _p(g), _p(_f32c(dx)), B, K, H, W, _stream())
+
+
+def _map_args(logits, wmap, y, keep, kind):
+    B, K, H, W = logits.shape
+    assert kind in MAP_KINDS, kind
+    assert 2 <= K <= SEG_MAX_K
+    keep = list(range(K)) if keep is None else list(keep)
+    assert keep and keep == sorted(set(keep)) and 0 <= keep[0] and keep[-1] < K
+    assert wmap is None or (wmap.shape == logits.shape and wmap.dtype == torch.float32 and wmap.is_contiguous() and wmap.is_cuda)
+    if kind == "squared":
+        assert y is not None and y.shape == logits.shape and y.is_contiguous() and y.is_cuda and y.dtype in (torch.float32, torch.float64)
+    else:
+        y = None
+    return B, K, H, W, keep_mask(keep), MAP_KINDS[kind], y
+
+
+def softmax_map_fwd(logits, wmap, y, keep, kind, table, partials=None):
+    """table (K fp64): 'linear' T_c = sum Wm_c p_c, 'squared' T_c = sum Wm_c (p_c - y_c)^2 over the classes ``keep`` (0 for the others);
+    Wm (B,K,H,W) fp32 or None = ones, y fp32 / fp64 (cmu_softmax_map_fwd)."""
+    B, K, H, W, mask, k, y = _map_args(logits, wmap, y, keep, kind)
+    assert table.dtype == torch.float64 and table.numel() == K and table.is_contiguous()
+    if partials is None:
+        partials = map_loss_partials(K, logits.device)
+    assert partials.dtype == torch.float64 and partials.numel() >= K * MAP_LOSS_MAX_BLOCKS and partials.is_contiguous()
+    call("cmu_softmax_map_fwd", _p(_f32c(logits)), _p(wmap), _p(y), int(y is not None and y.dtype == torch.float64), mask, k, _p(table),
+         _p(partials), B, K, H, W, _stream())
+
+
+def softmax_map_bwd(logits, wmap, y, keep, kind, g, dlogits):
+    """dlogits_j = p_j (G_j - sum_c p_c G_c), G_c = g_c Wm_c ('linear') or 2 g_c Wm_c (p_c - y_c) ('squared'); g: K fp64 on the device."""
+    B, K, H, W, mask, k, y = _map_args(logits, wmap, y, keep, kind)
+    assert g is None or (g.dtype == torch.float64 and g.numel() == K and g.is_contiguous())
+    assert dlogits.shape == logits.shape
+    call("cmu_softmax_map_bwd", _p(_f32c(logits)), _p(wmap), _p(y), int(y is not None and y.dtype == torch.float64), mask, k, _p(g),
+         _p(_f32c(dlogits)), B, K, H, W, _stream())
+
+
+def distance_field(d2_to, d2_from, field, plane, mode="signed", alpha=2.0, d2_to_b=None, d2_from_b=None):
+    """Plane ``plane`` of the (B,K,H,W) fp32 map ``field`` from the int32 squared distances of ``edt_rows`` to a set (``d2_to``) and to
+    its complement (``d2_from``): 'signed' -> sqrt(d2_to) outside the set, 1 - sqrt(d2_from) inside; 'unsigned' -> the distance to the
+    boundary to the power ``alpha``, plus that of a second pair when given.  An empty or a full set gives 0 (cmu_distance_field)."""
+    if mode not in FIELD_MODES:
+        raise ValueError(f"distance_field: mode must be 'signed' or 'unsigned', got {mode!r}")
+    B, H, W = _edt_check("distance_field", d2_to, torch.int32)
+    pairs = [d2_from] + ([] if d2_to_b is None and d2_from_b is None else [d2_to_b, d2_from_b])
+    for t in pairs:
+        if t is None or t.dtype != torch.int32 or t.shape != d2_to.shape or not t.is_contiguous() or t.device != d2_to.device:
+            raise ValueError(f"distance_field: every distance map must be a contiguous int32 tensor of shape {tuple(d2_to.shape)} on one device")
+    if len(pairs) == 3 and mode != "unsigned":
+        raise ValueError("distance_field: a second pair of maps belongs to mode 'unsigned'")
+    if mode == "unsigned" and not 0.0 < float(alpha) <= 16.0:
+        raise ValueError(f"distance_field: 0 < alpha <= 16, got {alpha!r}")
+    if (field.dim() != 4 or field.shape[0] != B or field.shape[2:] != (H, W) or field.dtype != torch.float32 or not field.is_contiguous()
+            or field.device != d2_to.device):
+        raise ValueError(f"distance_field: field must be a contiguous float32 (B,K,H,W) tensor over {(B, H, W)} on the maps' device")
+    K = field.shape[1]
+    if not 0 <= int(plane) < K:
+        raise ValueError(f"distance_field: plane {plane} of {K}")
+    call("cmu_distance_field", _p(d2_to), _p(d2_from), _p(d2_to_b), _p(d2_from_b), FIELD_MODES[mode], float(alpha), _p(field), int(plane),
+         B, K, H, W, _stream())
+    return field

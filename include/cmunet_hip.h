@@ -1042,6 +1042,56 @@ int cmu_hist_curves(const int64_t* counts, const uint64_t* conf, int rows, int N
  * when n % 16 == 0 and both pointers are 16-byte aligned, else one.                                                                  */
 int cmu_threshold_mask(const float* prob, float threshold, int v_pos, int v_neg, uint8_t* out, int64_t n, void* stream);
 
+/* ---------------------------------------------------------------------------------------------
+ * Losses for thin, rare foregrounds: focal cross entropy, map-weighted softmax sums (boundary and Hausdorff-DT losses) and the distance
+ * fields they take (csrc/map_loss.hip, csrc/map_loss_math.h; no reference counterpart).  x / logits (B,K,H,W)
+ * fp32, 2 <= K <= 8.  The conventions of cmu_seg_stats_fwd / cmu_index_ce_fwd: p is the fp32 softmax those entries use (the same bits);
+ * a lane takes 4 pixels (2 for K > 4) of every plane when H*W is a multiple of that and every tensor pointer of the call is 16-byte
+ * aligned, else 1 -- for the whole tensor; per-lane fp64 sums -> block partials -> a fixed-order finalisation; no floating-point
+ * atomics, the same bits on every call; upstream gradients g are read from device memory and NULL stands for zeros; no host sync.
+ * There is no workspace query: `partials` is a caller's fp64 tensor of columns x 1024 doubles (the grid is capped at 1,024 blocks;
+ * columns = 3 for cmu_focal_fwd, K for cmu_softmax_map_fwd).  It needs no initialisation: every element that is read was written by
+ * the same call.  Every element of every output is written on every call.
+ *
+ * cmu_focal_fwd: target_kind is a CMU_ICE_* code, the target as cmu_index_ce_fwd takes it (the arg-max of one-hot planes runs over all
+ * K channels).  class_w: K fp32 alpha_c or NULL (ones); gamma >= 0.  With t the pixel's label and q = 1 - p_t, formed as the sum of the
+ * OTHER classes' exponentials over the total (never 1 - p_t):
+ *   table[0] = sum alpha_t q^gamma (-log p_t)   -log p_t in the form of cmu_index_ce_fwd (with gamma = 0: its table[0], the same bits)
+ *   table[1] = sum alpha_t                      over the same pixels
+ *   table[2] = the number of pixels whose label is not ignore_index
+ * q^gamma is exactly 1 for gamma = 0 (also at q = 0), a multiplication for gamma = 1 and 2, else one fp32 exp(gamma log q), 0 at q = 0.
+ * A label outside [0, K) that is not ignore_index is never used as an index: it adds NaN to table[0] and gets a zero gradient.
+ * cmu_focal_bwd: g = 1 double (d / d table[0]);  dx_j = g alpha_t (d_jt - p_j) (gamma p_t q^(gamma-1) log p_t - q^gamma), zero at
+ * ignored pixels, evaluated without inf * 0 at q = 0 and without cancellation (both addends of an element have one sign).             */
+int cmu_focal_fwd(const float* x, const void* target, int target_kind, const float* class_w, double gamma, int64_t ignore_index,
+                  double* table, double* partials, int B, int K, int H, int W, void* stream);
+int cmu_focal_bwd(const float* x, const void* target, int target_kind, const float* class_w, double gamma, int64_t ignore_index,
+                  const double* g, float* dx, int B, int K, int H, int W, void* stream);
+/* cmu_softmax_map_fwd: table[K] doubles over the classes of keep_mask (bit c = class c; the wmap / y planes of the others are not read
+ * and their entries are 0).  wmap (B,K,H,W) fp32 or NULL (ones); y (B,K,H,W) fp32 / fp64 (y_is_f64), unused and nullable for kind 0.
+ *   kind 0 (linear)    table[c] = sum wmap_c p_c
+ *   kind 1 (squared)   table[c] = sum wmap_c (p_c - y_c)^2      the difference and the square in fp64; the difference is formed as
+ *                      ((1 - y_c) e_c - y_c sum_{j != c} e_j) / sum_j e_j from the exponentials behind p, so that against a one-hot y a
+ *                      confident pixel keeps its bits (p_c - 1 from the fp32 p would not)
+ * cmu_softmax_map_bwd: g = K doubles; dlogits_j = p_j (G_j - sum_c p_c G_c) with G_c = g_c wmap_c (kind 0) or 2 g_c wmap_c (p_c - y_c)
+ * (kind 1), G_c = 0 outside keep_mask; combined in fp64 as cmu_seg_stats_bwd does.  All K planes of dlogits are written.              */
+int cmu_softmax_map_fwd(const float* logits, const float* wmap, const void* y, int y_is_f64, int keep_mask, int kind, double* table,
+                        double* partials, int B, int K, int H, int W, void* stream);
+int cmu_softmax_map_bwd(const float* logits, const float* wmap, const void* y, int y_is_f64, int keep_mask, int kind, const double* g,
+                        float* dlogits, int B, int K, int H, int W, void* stream);
+/* cmu_distance_field: one fp32 plane of a (B,K,H,W) map, written at field + b K H W + plane H W, from the (B,H,W) int32 dist2 maps of
+ * cmu_edt_rows for a set S: d2_to = the transform to S (0 on S), d2_from = the transform to S's complement.  K >= 1.
+ *   mode 0 (signed; Kervadec's one_hot2dist)   outside S: sqrt(d2_to); inside S: 1 - sqrt(d2_from); in fp64, rounded once.  alpha and
+ *                                              the second pair are unused (NULL).
+ *   mode 1 (unsigned, MONAI's distance_field to the power alpha, 0 < alpha <= 16)   (sqrt(d2_to) + sqrt(d2_from))^alpha, of which one
+ *                                              root is 0: alpha = 2 is the integer d2 converted once, alpha = 1 its fp64 root rounded
+ *                                              once, else one fp32 exp((alpha / 2) log d2), 0 at d2 = 0.  A second pair (d2_to_b,
+ *                                              d2_from_b; both or neither) adds its own field: prediction plus target, one fp32 add.
+ * This library's rule for an empty or a full S -- either map of the pair holds -1, at every pixel of that image --: the plane, or in
+ * mode 1 that pair's addend, is 0 there.                                                                                              */
+int cmu_distance_field(const int32_t* d2_to, const int32_t* d2_from, const int32_t* d2_to_b, const int32_t* d2_from_b, int mode,
+                       double alpha, float* field, int plane, int B, int K, int H, int W, void* stream);
+
 /* Measurement support (bench.py's roofline block; no reference counterpart): the 16-bit MFMA rate this chip SUSTAINS.
  * Every wave of a one-workgroup-per-CU grid issues iters x 8 back-to-back 32x32x16 MFMAs from registers (no LDS, no
  * memory) or -- lds_fed = 1 -- the same MFMAs fed from LDS at the persistent conv kernel's ratio (6 fragment reads of 1 KB
