@@ -5,6 +5,7 @@
 // These are latency/HBM-bound: one pass per tensor, wave64 shuffle reductions (block_sum / block_sum_d / block_max, common.h),
 // fixed-order final sums.
 #include "common.h"
+#include "plane_stream.h"
 #include "seg_softmax.h"
 
 // ---------------------------------------------------------------------------------------------
@@ -276,31 +277,13 @@ extern "C" int cmu_softmax_ce_dice_fwd_bwd(const float* logits, const double* y1
 // ---------------------------------------------------------------------------------------------
 // softmax CE (probability targets, optional class weights) + per-class soft and thresholded Dice / IoU counters for 2..8 classes,
 // and the backward of the CE and of the SOFT counters (metrics.py:135-198 with any threshold / ignore_channels / beta / eps: the
-// scores are a few flops on these K-vectors, cmunet_amd/metrics.py).  The class count is compiled in as KT in {2, 4, 8} (classes
-// >= K masked, as the head kernels do); a lane takes V consecutive pixels of every plane (V = 4: 16-byte loads; V = 2 at KT = 8:
-// 8-byte logits / 16-byte fp64 target loads) when H*W % V == 0 and the pointers are 16-byte aligned, one pixel otherwise -- decided
-// for the whole tensor, no scalar tail behind a vector body.  HBM-bound: 4K + 8K (fp64 targets) bytes in per pixel, 4K more out backward.
-// ws: [1 + 5K columns][CE_MAX_BLOCKS] doubles, column-major so that the finalisation reads rows of blocks coalesced.
+// scores are a few flops on these K-vectors, cmunet_amd/metrics.py).  Streaming passes under the contract of plane_stream.h (V = 2
+// at KT = 8: 8-byte logits / 16-byte fp64 target loads).  HBM-bound: 4K + 8K (fp64 targets) bytes in per pixel, 4K more out backward.
+// ws: [1 + 5K columns][CE_MAX_BLOCKS] doubles, column-major so that the finalisation reads rows of blocks coalesced; it divides
+// column 0, the CE, by the pixel count.
 // table: [ce | tp_soft[K] | spr_soft[K] | tp_hard[K] | spr_hard[K] | sgt[K]] doubles.
 // ---------------------------------------------------------------------------------------------
 constexpr int SEG_MAX_K = 8;
-template <typename T, int V>
-struct alignas(sizeof(T) * V < 16 ? sizeof(T) * V : 16) SegVec {
-    T v[V];
-};
-// (image, first pixel) of pixel group g; ``small``: fewer than 2^31 groups (a 64-bit division is ~10x the instructions)
-__device__ static inline int64_t seg_group_base(int64_t g, int64_t gpi, bool small, int K, int64_t HW, int V) {
-    int64_t b, r;
-    if (small) {
-        const unsigned gu = (unsigned)g, bu = gu / (unsigned)gpi;
-        b = bu;
-        r = gu - bu * (unsigned)gpi;
-    } else {
-        b = g / gpi;
-        r = g - b * gpi;
-    }
-    return b * K * HW + r * V;
-}
 // seg_softmax<KT> (the pixel's fp32 softmax): seg_softmax.h, shared with the probability histogram of prob_hist.hip
 
 template <int KT, int V, typename TY>
@@ -318,14 +301,14 @@ __global__ __launch_bounds__(256) void seg_stats_kernel(const float* __restrict_
     const int64_t gpi = HW / V;
     const bool small = ngroups < (int64_t(1) << 31);
     for (int64_t g = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; g < ngroups; g += (int64_t)gridDim.x * blockDim.x) {
-        const int64_t base = seg_group_base(g, gpi, small, K, HW, V);
-        SegVec<float, V> lv[KT];
-        SegVec<TY, V> yv[KT];
+        const int64_t base = plane_group_base(g, gpi, small, K, HW, V);
+        PlaneVec<float, V> lv[KT];
+        PlaneVec<TY, V> yv[KT];
 #pragma unroll
         for (int c = 0; c < KT; ++c)
             if (c < K) {
-                lv[c] = *reinterpret_cast<const SegVec<float, V>*>(logits + base + c * HW);
-                yv[c] = *reinterpret_cast<const SegVec<TY, V>*>(y + base + c * HW);
+                lv[c] = *reinterpret_cast<const PlaneVec<float, V>*>(logits + base + c * HW);
+                yv[c] = *reinterpret_cast<const PlaneVec<TY, V>*>(y + base + c * HW);
             }
 #pragma unroll
         for (int v = 0; v < V; ++v) {
@@ -363,15 +346,6 @@ __global__ __launch_bounds__(256) void seg_stats_kernel(const float* __restrict_
             }
         }
 }
-// one wave per column, fixed order (lane l takes blocks l, l + 64, ...; then the wave's butterfly), as ce_dice_final_kernel
-__global__ __launch_bounds__(64) void seg_stats_final_kernel(const double* __restrict__ ws, int nblocks, double npix, double* __restrict__ table) {
-    const double* col = ws + (int64_t)blockIdx.x * CE_MAX_BLOCKS;
-    double s = 0.0;
-    for (int b = threadIdx.x; b < nblocks; b += 64) s += col[b];
-    s = wave_sum_d(s);
-    if (threadIdx.x == 0) table[blockIdx.x] = blockIdx.x == 0 ? s / npix : s;
-}
-
 template <int KT, int V, typename TY>
 __global__ __launch_bounds__(256) void seg_stats_bwd_kernel(const float* __restrict__ logits, const TY* __restrict__ y,
                                                            const float* __restrict__ class_w, const double* __restrict__ g_ce,
@@ -388,14 +362,14 @@ __global__ __launch_bounds__(256) void seg_stats_bwd_kernel(const float* __restr
     const int64_t gpi = HW / V;
     const bool small = ngroups < (int64_t(1) << 31);
     for (int64_t g = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; g < ngroups; g += (int64_t)gridDim.x * blockDim.x) {
-        const int64_t base = seg_group_base(g, gpi, small, K, HW, V);
-        SegVec<float, V> lv[KT], dv[KT];
-        SegVec<TY, V> yv[KT];
+        const int64_t base = plane_group_base(g, gpi, small, K, HW, V);
+        PlaneVec<float, V> lv[KT], dv[KT];
+        PlaneVec<TY, V> yv[KT];
 #pragma unroll
         for (int c = 0; c < KT; ++c)
             if (c < K) {
-                lv[c] = *reinterpret_cast<const SegVec<float, V>*>(logits + base + c * HW);
-                yv[c] = *reinterpret_cast<const SegVec<TY, V>*>(y + base + c * HW);
+                lv[c] = *reinterpret_cast<const PlaneVec<float, V>*>(logits + base + c * HW);
+                yv[c] = *reinterpret_cast<const PlaneVec<TY, V>*>(y + base + c * HW);
             }
 #pragma unroll
         for (int v = 0; v < V; ++v) {
@@ -420,18 +394,10 @@ __global__ __launch_bounds__(256) void seg_stats_bwd_kernel(const float* __restr
         }
 #pragma unroll
         for (int c = 0; c < KT; ++c)
-            if (c < K) *reinterpret_cast<SegVec<float, V>*>(dlogits + base + c * HW) = dv[c];
+            if (c < K) *reinterpret_cast<PlaneVec<float, V>*>(dlogits + base + c * HW) = dv[c];
     }
 }
 
-static inline int seg_grid(int64_t ngroups) {
-    const int64_t blocks = cmu_div_up64(ngroups, 256);
-    return (int)(blocks < CE_MAX_BLOCKS ? blocks : CE_MAX_BLOCKS);
-}
-// pixels per lane: 4 (2 at KT = 8, which keeps the K = 8 kernels clear of scratch) on whole 16-byte chunks of every plane, else 1
-static inline bool seg_vectorisable(int KT, int64_t HW, const void* a, const void* b, const void* c) {
-    return HW % (KT == 8 ? 2 : 4) == 0 && cmu_aligned16(a) && cmu_aligned16(b) && (c == nullptr || cmu_aligned16(c));
-}
 template <int KT, int V, typename TY>
 static void seg_fwd_launch(const float* logits, const void* y, const float* class_w, float thr, double* ws, int K, int64_t HW,
                            int64_t npix, int grid, hipStream_t st) {
@@ -443,19 +409,10 @@ static void seg_bwd_launch(const float* logits, const void* y, const float* clas
     hipLaunchKernelGGL((seg_stats_bwd_kernel<KT, V, TY>), dim3(grid), dim3(256), 0, st, logits, (const TY*)y, class_w, g_ce, g_tp, g_spr,
                        dlogits, K, HW, npix / V, (double)npix);
 }
-// FN<KT, V, TY>(args...) for the runtime class count, vector width and target type
-#define SEG_DISPATCH(FN, K, vec, f64, ...)                                                            \
-    do {                                                                                              \
-        if ((K) <= 2) {                                                                               \
-            if (vec) { if (f64) FN<2, 4, double>(__VA_ARGS__); else FN<2, 4, float>(__VA_ARGS__); }   \
-            else     { if (f64) FN<2, 1, double>(__VA_ARGS__); else FN<2, 1, float>(__VA_ARGS__); }   \
-        } else if ((K) <= 4) {                                                                        \
-            if (vec) { if (f64) FN<4, 4, double>(__VA_ARGS__); else FN<4, 4, float>(__VA_ARGS__); }   \
-            else     { if (f64) FN<4, 1, double>(__VA_ARGS__); else FN<4, 1, float>(__VA_ARGS__); }   \
-        } else {                                                                                      \
-            if (vec) { if (f64) FN<8, 2, double>(__VA_ARGS__); else FN<8, 2, float>(__VA_ARGS__); }   \
-            else     { if (f64) FN<8, 1, double>(__VA_ARGS__); else FN<8, 1, float>(__VA_ARGS__); }   \
-        }                                                                                             \
+// an INNER of PLANE_DISPATCH: FN<KT, V, TY>(args...) for the runtime target type
+#define SEG_DISPATCH_TY(KT, V, FN, f64, ...)                                              \
+    do {                                                                                  \
+        if (f64) FN<KT, V, double>(__VA_ARGS__); else FN<KT, V, float>(__VA_ARGS__);      \
     } while (0)
 
 extern "C" int64_t cmu_seg_stats_ws_bytes(int K) {
@@ -466,13 +423,12 @@ extern "C" int cmu_seg_stats_fwd(const float* logits, const void* y, int y_is_f6
     CMU_CHECK_ARG(logits && y && table && ws && B > 0 && H > 0 && W > 0, "cmu_seg_stats_fwd: bad args");
     CMU_CHECK_ARG(K >= 2 && K <= SEG_MAX_K, "cmu_seg_stats_fwd: 2 <= K <= %d classes (got %d)", SEG_MAX_K, K);
     hipStream_t st = (hipStream_t)stream;
-    const int64_t HW = (int64_t)H * W, npix = (int64_t)B * HW;
-    const int KT = K <= 2 ? 2 : K <= 4 ? 4 : 8;
-    const bool vec = seg_vectorisable(KT, HW, logits, y, nullptr);
-    const int grid = seg_grid(npix / (vec ? (KT == 8 ? 2 : 4) : 1));
-    SEG_DISPATCH(seg_fwd_launch, K, vec, y_is_f64 != 0, logits, y, class_w, threshold, (double*)ws, K, HW, npix, grid, st);
+    const PlaneStream ps = plane_stream(B, K, H, W, logits, y, nullptr, nullptr);
+    PLANE_DISPATCH(SEG_DISPATCH_TY, K, ps.V > 1, seg_fwd_launch, y_is_f64 != 0, logits, y, class_w, threshold, (double*)ws, K, ps.HW, ps.npix,
+                   ps.grid, st);
     CMU_CHECK_LAUNCH("cmu_seg_stats_fwd");
-    hipLaunchKernelGGL(seg_stats_final_kernel, dim3(1 + 5 * K), dim3(64), 0, st, (const double*)ws, grid, (double)npix, table);
+    hipLaunchKernelGGL(plane_final_kernel<true>, dim3(1 + 5 * K), dim3(64), 0, st, (const double*)ws, ps.grid, PLANE_ALL_COLUMNS, (double)ps.npix,
+                       table);
     CMU_CHECK_LAUNCH("cmu_seg_stats_fwd(final)");
     return CMU_OK;
 }
@@ -481,11 +437,9 @@ extern "C" int cmu_seg_stats_bwd(const float* logits, const void* y, int y_is_f6
     CMU_CHECK_ARG(logits && y && dlogits && B > 0 && H > 0 && W > 0, "cmu_seg_stats_bwd: bad args");
     CMU_CHECK_ARG(K >= 2 && K <= SEG_MAX_K, "cmu_seg_stats_bwd: 2 <= K <= %d classes (got %d)", SEG_MAX_K, K);
     hipStream_t st = (hipStream_t)stream;
-    const int64_t HW = (int64_t)H * W, npix = (int64_t)B * HW;
-    const int KT = K <= 2 ? 2 : K <= 4 ? 4 : 8;
-    const bool vec = seg_vectorisable(KT, HW, logits, y, dlogits);
-    const int grid = seg_grid(npix / (vec ? (KT == 8 ? 2 : 4) : 1));
-    SEG_DISPATCH(seg_bwd_launch, K, vec, y_is_f64 != 0, logits, y, class_w, g_ce, g_tp, g_spr, dlogits, K, HW, npix, grid, st);
+    const PlaneStream ps = plane_stream(B, K, H, W, logits, y, dlogits, nullptr);
+    PLANE_DISPATCH(SEG_DISPATCH_TY, K, ps.V > 1, seg_bwd_launch, y_is_f64 != 0, logits, y, class_w, g_ce, g_tp, g_spr, dlogits, K, ps.HW,
+                   ps.npix, ps.grid, st);
     CMU_CHECK_LAUNCH("cmu_seg_stats_bwd");
     return CMU_OK;
 }

@@ -2,52 +2,14 @@
 // counterpart): the focal cross entropy (Lin et al.), the map-weighted softmax sums behind the boundary loss (Kervadec et al.) and the
 // Hausdorff distance-transform loss (Karimi & Salcudean, as MONAI's HausdorffDTLoss states it), and the distance fields those two take
 // from the integer squared distances of cmu_edt_rows (edt.hip).
-// Streaming passes with the conventions of seg_stats_kernel (heads.hip) and ice_fwd_kernel (pointwise_loss.hip): p is seg_softmax<>()
-// (seg_softmax.h: the probability bits of the counters and the histogram), the class count is compiled in as KT in {2, 4, 8} with
-// classes >= K masked, a lane takes V = 4 / 4 / 2 consecutive pixels of every plane (16- / 8-byte accesses) when H*W % V == 0 and every
-// pointer is 16-byte aligned and ONE pixel otherwise -- decided for the whole tensor, no scalar tail behind a vector body --, per-lane
-// fp64 accumulation -> block partials -> a fixed-order finalisation kernel (no floating-point atomics: the same bits on every call), the
-// grid capped at CE_MAX_BLOCKS with grid-stride loops, 64-bit indexing, upstream gradients read from device memory (NULL = zeros).
-// The block partials live in a caller's fp64 tensor of [columns][CE_MAX_BLOCKS]; the finalisation reads the slots of the blocks that
-// were launched, each written by its block in the same call.
+// Streaming passes under the contract of plane_stream.h; p is seg_softmax<>() (seg_softmax.h: the probability bits of the counters and
+// the histogram).
 #include "common.h"
+#include "plane_stream.h"
 #include "seg_softmax.h"
 #include "map_loss_math.h"
 
 constexpr int ML_MAX_K = 8;
-template <typename T, int V>
-struct alignas(sizeof(T) * V < 16 ? sizeof(T) * V : 16) MlVec {
-    T v[V];
-};
-static inline int ml_grid(int64_t ngroups) {
-    const int64_t blocks = cmu_div_up64(ngroups, 256);
-    return (int)(blocks < CE_MAX_BLOCKS ? blocks : CE_MAX_BLOCKS);
-}
-// first pixel of pixel group g in plane 0 of its image (seg_group_base of heads.hip)
-__device__ static inline int64_t ml_group_base(int64_t g, int64_t gpi, bool small, int K, int64_t HW, int V) {
-    int64_t b, r;
-    if (small) {
-        const unsigned gu = (unsigned)g, bu = gu / (unsigned)gpi;
-        b = bu;
-        r = gu - bu * (unsigned)gpi;
-    } else {
-        b = g / gpi;
-        r = g - b * gpi;
-    }
-    return b * K * HW + r * V;
-}
-// one wave per column of partials ([column][CE_MAX_BLOCKS]), fixed order: lane l takes blocks l, l + 64, ...; then the wave's butterfly.
-// A column outside col_mask gives 0 and reads nothing.
-__global__ __launch_bounds__(64) void ml_final_kernel(const double* __restrict__ partials, int nblocks, unsigned col_mask,
-                                                      double* __restrict__ out) {
-    double s = 0.0;
-    if ((col_mask >> blockIdx.x) & 1u) {
-        const double* col = partials + (int64_t)blockIdx.x * CE_MAX_BLOCKS;
-        for (int b = threadIdx.x; b < nblocks; b += 64) s += col[b];
-        s = wave_sum_d(s);
-    }
-    if (threadIdx.x == 0) out[blockIdx.x] = s;
-}
 // The unnormalised exponentials behind seg_softmax's p, e_c = e^(l_c - max) -- its statements again, so the compiler merges the two --,
 // the first maximum am (e_am is exactly 1) and the sum of the OTHER e_c, in fp32 class order (rest32: what ice_log_softmax of
 // pointwise_loss.hip feeds log1p) and in fp64 (rest64: exact to 2^-53); sum_c e_c = rest64 + 1.
@@ -105,45 +67,9 @@ static inline int ml_check_shape(const char* who, int B, int K, int H, int W) {
 // is evaluated as  j == t: -g alpha_t (C + q q^gamma)   [d_tt - p_t = q]
 //                  j != t:  g alpha_t ((e_j / sum_{c != t} e_c) C + p_j q^gamma)   [p_j q^(gamma-1) = (e_j / sum) q^gamma; 0 / 0 := 0]
 // so nothing is inf * 0 at q = 0 with gamma < 1, and both addends of every element have one sign: no cancellation.
-// The target kinds are those of cmu_index_ce_fwd (CMU_ICE_*); the arg-max of one-hot planes runs over all K channels.  A label
+// The target kinds are those of cmu_index_ce_fwd (CMU_ICE_*); the arg-max of one-hot planes runs over all K channels (ALL_KEPT).  A label
 // outside [0, K) that is not ignore_index is never used as an index: NaN into table[0], a zero gradient.
 // ---------------------------------------------------------------------------------------------
-template <int TK> struct MlTarget;
-template <> struct MlTarget<CMU_ICE_LABEL_I64> { typedef int64_t T; static constexpr bool onehot = false; };
-template <> struct MlTarget<CMU_ICE_LABEL_I32> { typedef int32_t T; static constexpr bool onehot = false; };
-template <> struct MlTarget<CMU_ICE_LABEL_U8> { typedef uint8_t T; static constexpr bool onehot = false; };
-template <> struct MlTarget<CMU_ICE_LABEL_F32> { typedef float T; static constexpr bool onehot = false; };
-template <> struct MlTarget<CMU_ICE_LABEL_F64> { typedef double T; static constexpr bool onehot = false; };
-template <> struct MlTarget<CMU_ICE_ONEHOT_F32> { typedef float T; static constexpr bool onehot = true; };
-template <> struct MlTarget<CMU_ICE_ONEHOT_F64> { typedef double T; static constexpr bool onehot = true; };
-
-// labels of the V pixels of group g: the label plane's values truncated, or the arg-max over the K one-hot planes (first maximum)
-template <int KT, int V, int TK>
-__device__ static inline void ml_labels(const typename MlTarget<TK>::T* __restrict__ tgt, int64_t g, int64_t base, int K, int64_t HW,
-                                        int64_t (&lab)[V]) {
-    typedef typename MlTarget<TK>::T TT;
-    if (MlTarget<TK>::onehot) {
-        int best[V];
-        TT bv[V];
-#pragma unroll
-        for (int c = 0; c < KT; ++c)
-            if (c < K) {
-                const MlVec<TT, V> yv = *reinterpret_cast<const MlVec<TT, V>*>(tgt + base + c * HW);
-#pragma unroll
-                for (int v = 0; v < V; ++v)
-                    if (c == 0 || yv.v[v] > bv[v]) {
-                        best[v] = c;
-                        bv[v] = yv.v[v];
-                    }
-            }
-#pragma unroll
-        for (int v = 0; v < V; ++v) lab[v] = best[v];
-    } else {
-        const MlVec<TT, V> tv = *reinterpret_cast<const MlVec<TT, V>*>(tgt + g * V);
-#pragma unroll
-        for (int v = 0; v < V; ++v) lab[v] = (int64_t)tv.v[v];
-    }
-}
 // one pixel with label t in [0, K): p = seg_softmax, e = the unnormalised exponentials (the statements of seg_softmax again: the
 // compiler merges them), pt = p_t, nlp = -log p_t, so = sum of e_c over c != t, q = so / sum of e_c
 template <int KT>
@@ -168,7 +94,7 @@ __device__ static inline void ml_focal_pixel(const float (&l)[KT], int K, int t,
 }
 
 template <int KT, int V, int TK>
-__global__ __launch_bounds__(256) void ml_focal_fwd_kernel(const float* __restrict__ x, const typename MlTarget<TK>::T* __restrict__ tgt,
+__global__ __launch_bounds__(256) void ml_focal_fwd_kernel(const float* __restrict__ x, const typename PlaneTarget<TK>::T* __restrict__ tgt,
                                                           const float* __restrict__ class_w, double* __restrict__ partials, int K,
                                                           int64_t HW, int64_t ngroups, double gamma, int64_t ignore_index) {
     __shared__ double red[4];
@@ -178,13 +104,13 @@ __global__ __launch_bounds__(256) void ml_focal_fwd_kernel(const float* __restri
     const int64_t gpi = HW / V;
     const bool small = ngroups < (int64_t(1) << 31);
     for (int64_t g = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; g < ngroups; g += (int64_t)gridDim.x * blockDim.x) {
-        const int64_t base = ml_group_base(g, gpi, small, K, HW, V);
-        MlVec<float, V> xv[KT];
+        const int64_t base = plane_group_base(g, gpi, small, K, HW, V);
+        PlaneVec<float, V> xv[KT];
 #pragma unroll
         for (int c = 0; c < KT; ++c)
-            if (c < K) xv[c] = *reinterpret_cast<const MlVec<float, V>*>(x + base + c * HW);
+            if (c < K) xv[c] = *reinterpret_cast<const PlaneVec<float, V>*>(x + base + c * HW);
         int64_t lab[V];
-        ml_labels<KT, V, TK>(tgt, g, base, K, HW, lab);
+        plane_labels<KT, V, TK, true>(tgt, g, base, K, HW, 0u, lab);
 #pragma unroll
         for (int v = 0; v < V; ++v) {
             const int64_t t = lab[v];
@@ -216,7 +142,7 @@ __global__ __launch_bounds__(256) void ml_focal_fwd_kernel(const float* __restri
     }
 }
 template <int KT, int V, int TK>
-__global__ __launch_bounds__(256) void ml_focal_bwd_kernel(const float* __restrict__ x, const typename MlTarget<TK>::T* __restrict__ tgt,
+__global__ __launch_bounds__(256) void ml_focal_bwd_kernel(const float* __restrict__ x, const typename PlaneTarget<TK>::T* __restrict__ tgt,
                                                           const float* __restrict__ class_w, const double* __restrict__ g_up,
                                                           float* __restrict__ dx, int K, int64_t HW, int64_t ngroups, double gamma,
                                                           int64_t ignore_index) {
@@ -227,13 +153,13 @@ __global__ __launch_bounds__(256) void ml_focal_bwd_kernel(const float* __restri
     const int64_t gpi = HW / V;
     const bool small = ngroups < (int64_t(1) << 31);
     for (int64_t g = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; g < ngroups; g += (int64_t)gridDim.x * blockDim.x) {
-        const int64_t base = ml_group_base(g, gpi, small, K, HW, V);
-        MlVec<float, V> xv[KT], dv[KT];
+        const int64_t base = plane_group_base(g, gpi, small, K, HW, V);
+        PlaneVec<float, V> xv[KT], dv[KT];
 #pragma unroll
         for (int c = 0; c < KT; ++c)
-            if (c < K) xv[c] = *reinterpret_cast<const MlVec<float, V>*>(x + base + c * HW);
+            if (c < K) xv[c] = *reinterpret_cast<const PlaneVec<float, V>*>(x + base + c * HW);
         int64_t lab[V];
-        ml_labels<KT, V, TK>(tgt, g, base, K, HW, lab);
+        plane_labels<KT, V, TK, true>(tgt, g, base, K, HW, 0u, lab);
 #pragma unroll
         for (int v = 0; v < V; ++v) {
             const int64_t t = lab[v];
@@ -259,46 +185,21 @@ __global__ __launch_bounds__(256) void ml_focal_bwd_kernel(const float* __restri
         }
 #pragma unroll
         for (int c = 0; c < KT; ++c)
-            if (c < K) *reinterpret_cast<MlVec<float, V>*>(dx + base + c * HW) = dv[c];
+            if (c < K) *reinterpret_cast<PlaneVec<float, V>*>(dx + base + c * HW) = dv[c];
     }
 }
 
 template <int KT, int V, int TK>
 static void ml_focal_fwd_launch(const float* x, const void* tgt, const float* class_w, double* partials, int K, int64_t HW, int64_t npix,
                                 double gamma, int64_t ignore_index, int grid, hipStream_t st) {
-    hipLaunchKernelGGL((ml_focal_fwd_kernel<KT, V, TK>), dim3(grid), dim3(256), 0, st, x, (const typename MlTarget<TK>::T*)tgt, class_w,
+    hipLaunchKernelGGL((ml_focal_fwd_kernel<KT, V, TK>), dim3(grid), dim3(256), 0, st, x, (const typename PlaneTarget<TK>::T*)tgt, class_w,
                        partials, K, HW, npix / V, gamma, ignore_index);
 }
 template <int KT, int V, int TK>
 static void ml_focal_bwd_launch(const float* x, const void* tgt, const float* class_w, const double* g, float* dx, int K, int64_t HW,
                                 int64_t npix, double gamma, int64_t ignore_index, int grid, hipStream_t st) {
-    hipLaunchKernelGGL((ml_focal_bwd_kernel<KT, V, TK>), dim3(grid), dim3(256), 0, st, x, (const typename MlTarget<TK>::T*)tgt, class_w, g, dx,
+    hipLaunchKernelGGL((ml_focal_bwd_kernel<KT, V, TK>), dim3(grid), dim3(256), 0, st, x, (const typename PlaneTarget<TK>::T*)tgt, class_w, g, dx,
                        K, HW, npix / V, gamma, ignore_index);
-}
-// FN<KT, V, TK>(args...) for the runtime class count, vector width and target kind
-#define ML_DISPATCH_TK(FN, KT, V, tk, ...)                                                     \
-    do {                                                                                       \
-        switch (tk) {                                                                          \
-            case CMU_ICE_LABEL_I64: FN<KT, V, CMU_ICE_LABEL_I64>(__VA_ARGS__); break;          \
-            case CMU_ICE_LABEL_I32: FN<KT, V, CMU_ICE_LABEL_I32>(__VA_ARGS__); break;          \
-            case CMU_ICE_LABEL_U8: FN<KT, V, CMU_ICE_LABEL_U8>(__VA_ARGS__); break;            \
-            case CMU_ICE_LABEL_F32: FN<KT, V, CMU_ICE_LABEL_F32>(__VA_ARGS__); break;          \
-            case CMU_ICE_LABEL_F64: FN<KT, V, CMU_ICE_LABEL_F64>(__VA_ARGS__); break;          \
-            case CMU_ICE_ONEHOT_F32: FN<KT, V, CMU_ICE_ONEHOT_F32>(__VA_ARGS__); break;        \
-            default: FN<KT, V, CMU_ICE_ONEHOT_F64>(__VA_ARGS__);                               \
-        }                                                                                      \
-    } while (0)
-#define ML_DISPATCH_FOCAL(FN, K, vec, tk, ...)                                                                                   \
-    do {                                                                                                                         \
-        if ((K) <= 2)      { if (vec) ML_DISPATCH_TK(FN, 2, 4, tk, __VA_ARGS__); else ML_DISPATCH_TK(FN, 2, 1, tk, __VA_ARGS__); } \
-        else if ((K) <= 4) { if (vec) ML_DISPATCH_TK(FN, 4, 4, tk, __VA_ARGS__); else ML_DISPATCH_TK(FN, 4, 1, tk, __VA_ARGS__); } \
-        else               { if (vec) ML_DISPATCH_TK(FN, 8, 2, tk, __VA_ARGS__); else ML_DISPATCH_TK(FN, 8, 1, tk, __VA_ARGS__); } \
-    } while (0)
-
-// pixels per lane: 4 (2 at K > 4) on whole 16- / 8-byte chunks of every plane with 16-byte aligned pointers (NULL: not used), else 1
-static inline int ml_width(int K, int64_t HW, const void* a, const void* b, const void* c, const void* d) {
-    const int V = K > 4 ? 2 : 4;
-    return (HW % V == 0 && cmu_aligned16(a) && cmu_aligned16(b) && cmu_aligned16(c) && cmu_aligned16(d)) ? V : 1;
 }
 static int ml_focal_check(const char* who, const void* x, const void* tgt, int target_kind, double gamma, int B, int K, int H, int W) {
     if (int rc = ml_check_shape(who, B, K, H, W)) return rc;
@@ -312,12 +213,11 @@ extern "C" int cmu_focal_fwd(const float* x, const void* target, int target_kind
     if (int rc = ml_focal_check("cmu_focal_fwd", x, target, target_kind, gamma, B, K, H, W)) return rc;
     CMU_CHECK_ARG(table && partials, "cmu_focal_fwd: bad args");
     hipStream_t st = (hipStream_t)stream;
-    const int64_t HW = (int64_t)H * W, npix = (int64_t)B * HW;
-    const int V = ml_width(K, HW, x, target, nullptr, nullptr);
-    const int grid = ml_grid(npix / V);
-    ML_DISPATCH_FOCAL(ml_focal_fwd_launch, K, V > 1, target_kind, x, target, class_w, partials, K, HW, npix, gamma, ignore_index, grid, st);
+    const PlaneStream ps = plane_stream(B, K, H, W, x, target, nullptr, nullptr);
+    PLANE_DISPATCH(PLANE_DISPATCH_TK, K, ps.V > 1, ml_focal_fwd_launch, target_kind, x, target, class_w, partials, K, ps.HW, ps.npix, gamma,
+                   ignore_index, ps.grid, st);
     CMU_CHECK_LAUNCH("cmu_focal_fwd");
-    hipLaunchKernelGGL(ml_final_kernel, dim3(3), dim3(64), 0, st, (const double*)partials, grid, 7u, table);
+    hipLaunchKernelGGL(plane_final_kernel<false>, dim3(3), dim3(64), 0, st, (const double*)partials, ps.grid, 7ull, 1.0, table);
     CMU_CHECK_LAUNCH("cmu_focal_fwd(final)");
     return CMU_OK;
 }
@@ -326,10 +226,9 @@ extern "C" int cmu_focal_bwd(const float* x, const void* target, int target_kind
     if (int rc = ml_focal_check("cmu_focal_bwd", x, target, target_kind, gamma, B, K, H, W)) return rc;
     CMU_CHECK_ARG(dx, "cmu_focal_bwd: bad args");
     hipStream_t st = (hipStream_t)stream;
-    const int64_t HW = (int64_t)H * W, npix = (int64_t)B * HW;
-    const int V = ml_width(K, HW, x, target, dx, nullptr);
-    const int grid = ml_grid(npix / V);
-    ML_DISPATCH_FOCAL(ml_focal_bwd_launch, K, V > 1, target_kind, x, target, class_w, g, dx, K, HW, npix, gamma, ignore_index, grid, st);
+    const PlaneStream ps = plane_stream(B, K, H, W, x, target, dx, nullptr);
+    PLANE_DISPATCH(PLANE_DISPATCH_TK, K, ps.V > 1, ml_focal_bwd_launch, target_kind, x, target, class_w, g, dx, K, ps.HW, ps.npix, gamma,
+                   ignore_index, ps.grid, st);
     CMU_CHECK_LAUNCH("cmu_focal_bwd");
     return CMU_OK;
 }
@@ -360,16 +259,16 @@ __global__ __launch_bounds__(256) void ml_map_fwd_kernel(const float* __restrict
     const int64_t gpi = HW / V;
     const bool small = ngroups < (int64_t(1) << 31);
     for (int64_t g = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; g < ngroups; g += (int64_t)gridDim.x * blockDim.x) {
-        const int64_t base = ml_group_base(g, gpi, small, K, HW, V);
-        MlVec<float, V> lv[KT], wv[KT];
-        MlVec<TY, V> yv[KT];
+        const int64_t base = plane_group_base(g, gpi, small, K, HW, V);
+        PlaneVec<float, V> lv[KT], wv[KT];
+        PlaneVec<TY, V> yv[KT];
 #pragma unroll
         for (int c = 0; c < KT; ++c)
             if (c < K) {
-                lv[c] = *reinterpret_cast<const MlVec<float, V>*>(logits + base + c * HW);
+                lv[c] = *reinterpret_cast<const PlaneVec<float, V>*>(logits + base + c * HW);
                 if ((keep_mask >> c) & 1u) {
-                    if (wmap) wv[c] = *reinterpret_cast<const MlVec<float, V>*>(wmap + base + c * HW);
-                    if (KIND == 1) yv[c] = *reinterpret_cast<const MlVec<TY, V>*>(y + base + c * HW);
+                    if (wmap) wv[c] = *reinterpret_cast<const PlaneVec<float, V>*>(wmap + base + c * HW);
+                    if (KIND == 1) yv[c] = *reinterpret_cast<const PlaneVec<TY, V>*>(y + base + c * HW);
                 }
             }
 #pragma unroll
@@ -414,16 +313,16 @@ __global__ __launch_bounds__(256) void ml_map_bwd_kernel(const float* __restrict
     const int64_t gpi = HW / V;
     const bool small = ngroups < (int64_t(1) << 31);
     for (int64_t g = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; g < ngroups; g += (int64_t)gridDim.x * blockDim.x) {
-        const int64_t base = ml_group_base(g, gpi, small, K, HW, V);
-        MlVec<float, V> lv[KT], wv[KT], dv[KT];
-        MlVec<TY, V> yv[KT];
+        const int64_t base = plane_group_base(g, gpi, small, K, HW, V);
+        PlaneVec<float, V> lv[KT], wv[KT], dv[KT];
+        PlaneVec<TY, V> yv[KT];
 #pragma unroll
         for (int c = 0; c < KT; ++c)
             if (c < K) {
-                lv[c] = *reinterpret_cast<const MlVec<float, V>*>(logits + base + c * HW);
+                lv[c] = *reinterpret_cast<const PlaneVec<float, V>*>(logits + base + c * HW);
                 if ((keep_mask >> c) & 1u) {
-                    if (wmap) wv[c] = *reinterpret_cast<const MlVec<float, V>*>(wmap + base + c * HW);
-                    if (KIND == 1) yv[c] = *reinterpret_cast<const MlVec<TY, V>*>(y + base + c * HW);
+                    if (wmap) wv[c] = *reinterpret_cast<const PlaneVec<float, V>*>(wmap + base + c * HW);
+                    if (KIND == 1) yv[c] = *reinterpret_cast<const PlaneVec<TY, V>*>(y + base + c * HW);
                 }
             }
 #pragma unroll
@@ -453,7 +352,7 @@ __global__ __launch_bounds__(256) void ml_map_bwd_kernel(const float* __restrict
         }
 #pragma unroll
         for (int c = 0; c < KT; ++c)
-            if (c < K) *reinterpret_cast<MlVec<float, V>*>(dlogits + base + c * HW) = dv[c];
+            if (c < K) *reinterpret_cast<PlaneVec<float, V>*>(dlogits + base + c * HW) = dv[c];
     }
 }
 
@@ -469,18 +368,12 @@ static void ml_map_bwd_launch(const float* logits, const float* wmap, const void
     hipLaunchKernelGGL((ml_map_bwd_kernel<KT, V, KIND, TY>), dim3(grid), dim3(256), 0, st, logits, wmap, (const TY*)y, g, dlogits, K, HW,
                        npix / V, keep_mask);
 }
-// FN<KT, V, KIND, TY>(args...) for the runtime class count, vector width, kind and target type (kind 0 reads no target)
-#define ML_DISPATCH_KY(FN, KT, V, kind, f64, ...)                                      \
+// an INNER of PLANE_DISPATCH: FN<KT, V, KIND, TY>(args...) for the runtime kind and target type (kind 0 reads no target)
+#define ML_DISPATCH_KY(KT, V, FN, kind, f64, ...)                                      \
     do {                                                                               \
         if ((kind) == 0) FN<KT, V, 0, float>(__VA_ARGS__);                             \
         else if (f64) FN<KT, V, 1, double>(__VA_ARGS__);                               \
         else FN<KT, V, 1, float>(__VA_ARGS__);                                         \
-    } while (0)
-#define ML_DISPATCH_MAP(FN, K, vec, kind, f64, ...)                                                                                          \
-    do {                                                                                                                                     \
-        if ((K) <= 2)      { if (vec) ML_DISPATCH_KY(FN, 2, 4, kind, f64, __VA_ARGS__); else ML_DISPATCH_KY(FN, 2, 1, kind, f64, __VA_ARGS__); } \
-        else if ((K) <= 4) { if (vec) ML_DISPATCH_KY(FN, 4, 4, kind, f64, __VA_ARGS__); else ML_DISPATCH_KY(FN, 4, 1, kind, f64, __VA_ARGS__); } \
-        else               { if (vec) ML_DISPATCH_KY(FN, 8, 2, kind, f64, __VA_ARGS__); else ML_DISPATCH_KY(FN, 8, 1, kind, f64, __VA_ARGS__); } \
     } while (0)
 
 static int ml_map_check(const char* who, const void* logits, const void* y, int keep_mask, int kind, int B, int K, int H, int W) {
@@ -495,12 +388,12 @@ extern "C" int cmu_softmax_map_fwd(const float* logits, const float* wmap, const
     if (int rc = ml_map_check("cmu_softmax_map_fwd", logits, y, keep_mask, kind, B, K, H, W)) return rc;
     CMU_CHECK_ARG(table && partials, "cmu_softmax_map_fwd: bad args");
     hipStream_t st = (hipStream_t)stream;
-    const int64_t HW = (int64_t)H * W, npix = (int64_t)B * HW;
-    const int V = ml_width(K, HW, logits, wmap, kind == 1 ? y : nullptr, nullptr);
-    const int grid = ml_grid(npix / V);
-    ML_DISPATCH_MAP(ml_map_fwd_launch, K, V > 1, kind, y_is_f64 != 0, logits, wmap, y, partials, K, HW, npix, (unsigned)keep_mask, grid, st);
+    const PlaneStream ps = plane_stream(B, K, H, W, logits, wmap, kind == 1 ? y : nullptr, nullptr);
+    PLANE_DISPATCH(ML_DISPATCH_KY, K, ps.V > 1, ml_map_fwd_launch, kind, y_is_f64 != 0, logits, wmap, y, partials, K, ps.HW, ps.npix,
+                   (unsigned)keep_mask, ps.grid, st);
     CMU_CHECK_LAUNCH("cmu_softmax_map_fwd");
-    hipLaunchKernelGGL(ml_final_kernel, dim3(K), dim3(64), 0, st, (const double*)partials, grid, (unsigned)keep_mask, table);
+    hipLaunchKernelGGL(plane_final_kernel<false>, dim3(K), dim3(64), 0, st, (const double*)partials, ps.grid, (unsigned long long)keep_mask,
+                       1.0, table);
     CMU_CHECK_LAUNCH("cmu_softmax_map_fwd(final)");
     return CMU_OK;
 }
@@ -509,10 +402,9 @@ extern "C" int cmu_softmax_map_bwd(const float* logits, const float* wmap, const
     if (int rc = ml_map_check("cmu_softmax_map_bwd", logits, y, keep_mask, kind, B, K, H, W)) return rc;
     CMU_CHECK_ARG(dlogits, "cmu_softmax_map_bwd: bad args");
     hipStream_t st = (hipStream_t)stream;
-    const int64_t HW = (int64_t)H * W, npix = (int64_t)B * HW;
-    const int V = ml_width(K, HW, logits, wmap, kind == 1 ? y : nullptr, dlogits);
-    const int grid = ml_grid(npix / V);
-    ML_DISPATCH_MAP(ml_map_bwd_launch, K, V > 1, kind, y_is_f64 != 0, logits, wmap, y, g, dlogits, K, HW, npix, (unsigned)keep_mask, grid, st);
+    const PlaneStream ps = plane_stream(B, K, H, W, logits, wmap, kind == 1 ? y : nullptr, dlogits);
+    PLANE_DISPATCH(ML_DISPATCH_KY, K, ps.V > 1, ml_map_bwd_launch, kind, y_is_f64 != 0, logits, wmap, y, g, dlogits, K, ps.HW, ps.npix,
+                   (unsigned)keep_mask, ps.grid, st);
     CMU_CHECK_LAUNCH("cmu_softmax_map_bwd");
     return CMU_OK;
 }
@@ -531,10 +423,10 @@ __global__ __launch_bounds__(256) void ml_field_kernel(const int32_t* __restrict
     const int64_t gpi = HW / V;
     const bool small = ngroups < (int64_t(1) << 31);
     for (int64_t g = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; g < ngroups; g += (int64_t)gridDim.x * blockDim.x) {
-        const int64_t out = ml_group_base(g, gpi, small, K, HW, V) + plane * HW;
-        const MlVec<int32_t, V> ta = *reinterpret_cast<const MlVec<int32_t, V>*>(to_a + g * V);
-        const MlVec<int32_t, V> fa = *reinterpret_cast<const MlVec<int32_t, V>*>(from_a + g * V);
-        MlVec<float, V> f;
+        const int64_t out = plane_group_base(g, gpi, small, K, HW, V) + plane * HW;
+        const PlaneVec<int32_t, V> ta = *reinterpret_cast<const PlaneVec<int32_t, V>*>(to_a + g * V);
+        const PlaneVec<int32_t, V> fa = *reinterpret_cast<const PlaneVec<int32_t, V>*>(from_a + g * V);
+        PlaneVec<float, V> f;
         if (mode == 0) {
 #pragma unroll
             for (int v = 0; v < V; ++v) f.v[v] = cmu_ml_signed_field(ta.v[v], fa.v[v]);
@@ -542,13 +434,13 @@ __global__ __launch_bounds__(256) void ml_field_kernel(const int32_t* __restrict
 #pragma unroll
             for (int v = 0; v < V; ++v) f.v[v] = cmu_ml_unsigned_field(ta.v[v], fa.v[v], alpha);
             if (to_b) {
-                const MlVec<int32_t, V> tb = *reinterpret_cast<const MlVec<int32_t, V>*>(to_b + g * V);
-                const MlVec<int32_t, V> fb = *reinterpret_cast<const MlVec<int32_t, V>*>(from_b + g * V);
+                const PlaneVec<int32_t, V> tb = *reinterpret_cast<const PlaneVec<int32_t, V>*>(to_b + g * V);
+                const PlaneVec<int32_t, V> fb = *reinterpret_cast<const PlaneVec<int32_t, V>*>(from_b + g * V);
 #pragma unroll
                 for (int v = 0; v < V; ++v) f.v[v] = f.v[v] + cmu_ml_unsigned_field(tb.v[v], fb.v[v], alpha);
             }
         }
-        *reinterpret_cast<MlVec<float, V>*>(field + out) = f;
+        *reinterpret_cast<PlaneVec<float, V>*>(field + out) = f;
     }
 }
 extern "C" int cmu_distance_field(const int32_t* d2_to, const int32_t* d2_from, const int32_t* d2_to_b, const int32_t* d2_from_b, int mode,
@@ -563,7 +455,7 @@ extern "C" int cmu_distance_field(const int32_t* d2_to, const int32_t* d2_from, 
     const int64_t HW = (int64_t)H * W, npix = (int64_t)B * HW;
     const bool vec = HW % 4 == 0 && cmu_aligned16(d2_to) && cmu_aligned16(d2_from) && cmu_aligned16(d2_to_b) && cmu_aligned16(d2_from_b) &&
                      cmu_aligned16(field);
-    const int grid = ml_grid(npix / (vec ? 4 : 1));
+    const int grid = plane_grid(npix / (vec ? 4 : 1));
     if (vec)
         hipLaunchKernelGGL(ml_field_kernel<4>, dim3(grid), dim3(256), 0, st, d2_to, d2_from, d2_to_b, d2_from_b, mode, alpha, field, plane, K, HW,
                            npix / 4);

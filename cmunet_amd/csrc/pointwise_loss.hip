@@ -1,31 +1,12 @@
 // pointwise_loss.hip -- the element-wise losses (L1 / MSE / BCE / BCE-with-logits) and the class-index cross entropy of
-// Finetuning/metrics.py:495-551 (bare subclasses of the torch.nn losses) as streaming passes with the conventions of
-// seg_stats_kernel / seg_stats_bwd_kernel (heads.hip): fp32 predictions, targets read in their own dtype, per-lane fp64 accumulation
-// -> block partials in a workspace -> a fixed-order finalisation kernel (no floating-point atomics: the same bits every call), the
-// access width chosen ONCE for the whole tensor (no scalar tail behind a vector body, a vector never straddles a channel plane), the
-// grid capped at CE_MAX_BLOCKS with grid-stride loops, 64-bit indexing, and backward kernels that read their upstream gradients from
-// device memory (no host synchronisation anywhere).
+// Finetuning/metrics.py:495-551 (bare subclasses of the torch.nn losses) as streaming passes under the contract of plane_stream.h:
+// fp32 predictions, targets read in their own dtype.  The element-wise family walks a flat (outer, C, inner) tensor and takes the
+// contract's grid cap, partials and finalisation; its width rule is its own (below).
 #include "common.h"
+#include "plane_stream.h"
 
 constexpr int PWL_MAX_C = 8;             // channels of the per-channel weight vectors; classes of the index CE
 static_assert(PWL_MAX_C == CMU_PWL_MAX_C, "header constant");
-
-template <typename T, int V>
-struct alignas(sizeof(T) * V < 16 ? sizeof(T) * V : 16) PwVec {
-    T v[V];
-};
-static inline int pw_grid(int64_t ngroups) {
-    const int64_t blocks = cmu_div_up64(ngroups, 256);
-    return (int)(blocks < CE_MAX_BLOCKS ? blocks : CE_MAX_BLOCKS);
-}
-// one wave per column of ws ([column][CE_MAX_BLOCKS]), fixed order: lane l takes blocks l, l + 64, ...; then the wave's butterfly
-__global__ __launch_bounds__(64) void pw_final_kernel(const double* __restrict__ ws, int nblocks, double* __restrict__ out) {
-    const double* col = ws + (int64_t)blockIdx.x * CE_MAX_BLOCKS;
-    double s = 0.0;
-    for (int b = threadIdx.x; b < nblocks; b += 64) s += col[b];
-    s = wave_sum_d(s);
-    if (threadIdx.x == 0) out[blockIdx.x] = s;
-}
 
 // ---------------------------------------------------------------------------------------------
 // (a) element-wise family.  The tensor is (outer, C, inner); the optional per-channel fp32 vectors chan_w / chan_pw are indexed by
@@ -98,8 +79,8 @@ __global__ __launch_bounds__(256) void pw_fwd_kernel(const float* __restrict__ x
         const int64_t i0 = g * V;
         const int c = pw_channel(i0, inner, C, small);
         const double w = chan_w ? (double)chan_w[c] : 1.0, pw = chan_pw ? (double)chan_pw[c] : 1.0;
-        const PwVec<float, V> xv = *reinterpret_cast<const PwVec<float, V>*>(x + i0);
-        const PwVec<TY, V> yv = *reinterpret_cast<const PwVec<TY, V>*>(y + i0);
+        const PlaneVec<float, V> xv = *reinterpret_cast<const PlaneVec<float, V>*>(x + i0);
+        const PlaneVec<TY, V> yv = *reinterpret_cast<const PlaneVec<TY, V>*>(y + i0);
         double t = 0.0;
 #pragma unroll
         for (int v = 0; v < V; ++v) t += pw_term<KIND>(xv.v[v], (double)yv.v[v], pw);
@@ -118,12 +99,12 @@ __global__ __launch_bounds__(256) void pw_bwd_kernel(const float* __restrict__ x
         const int64_t i0 = g * V;
         const int c = pw_channel(i0, inner, C, small);
         const double gw = g0 * (chan_w ? (double)chan_w[c] : 1.0), pw = chan_pw ? (double)chan_pw[c] : 1.0;
-        const PwVec<float, V> xv = *reinterpret_cast<const PwVec<float, V>*>(x + i0);
-        const PwVec<TY, V> yv = *reinterpret_cast<const PwVec<TY, V>*>(y + i0);
-        PwVec<float, V> dv;
+        const PlaneVec<float, V> xv = *reinterpret_cast<const PlaneVec<float, V>*>(x + i0);
+        const PlaneVec<TY, V> yv = *reinterpret_cast<const PlaneVec<TY, V>*>(y + i0);
+        PlaneVec<float, V> dv;
 #pragma unroll
         for (int v = 0; v < V; ++v) dv.v[v] = (float)(gw * pw_dterm<KIND>(xv.v[v], (double)yv.v[v], pw));
-        *reinterpret_cast<PwVec<float, V>*>(dx + i0) = dv;
+        *reinterpret_cast<PlaneVec<float, V>*>(dx + i0) = dv;
     }
 }
 
@@ -168,10 +149,10 @@ extern "C" int cmu_pointwise_loss_fwd(int kind, const float* x, const void* y, i
     hipStream_t st = (hipStream_t)stream;
     const int64_t n = outer * C * inner;
     const bool vec = inner % 4 == 0 && cmu_aligned16(x) && cmu_aligned16(y);
-    const int grid = pw_grid(n / (vec ? 4 : 1));
+    const int grid = plane_grid(n / (vec ? 4 : 1));
     PW_DISPATCH(pw_fwd_launch, kind, vec, y_is_f64 != 0, x, y, chan_w, chan_pw, (double*)ws, C, inner, n, grid, st);
     CMU_CHECK_LAUNCH("cmu_pointwise_loss_fwd");
-    hipLaunchKernelGGL(pw_final_kernel, dim3(1), dim3(64), 0, st, (const double*)ws, grid, out);
+    hipLaunchKernelGGL(plane_final_kernel<false>, dim3(1), dim3(64), 0, st, (const double*)ws, grid, PLANE_ALL_COLUMNS, 1.0, out);
     CMU_CHECK_LAUNCH("cmu_pointwise_loss_fwd(final)");
     return CMU_OK;
 }
@@ -182,46 +163,23 @@ extern "C" int cmu_pointwise_loss_bwd(int kind, const float* x, const void* y, i
     hipStream_t st = (hipStream_t)stream;
     const int64_t n = outer * C * inner;
     const bool vec = inner % 4 == 0 && cmu_aligned16(x) && cmu_aligned16(y) && cmu_aligned16(dx);
-    const int grid = pw_grid(n / (vec ? 4 : 1));
+    const int grid = plane_grid(n / (vec ? 4 : 1));
     PW_DISPATCH(pw_bwd_launch, kind, vec, y_is_f64 != 0, x, y, chan_w, chan_pw, g, dx, C, inner, n, grid, st);
     CMU_CHECK_LAUNCH("cmu_pointwise_loss_bwd");
     return CMU_OK;
 }
 
 // ---------------------------------------------------------------------------------------------
-// (b) class-index cross entropy of (B,K,H,W) fp32 input, 2 <= K <= 8 (compiled class counts KT in {2, 4, 8}, classes >= K masked, and
-// pixels per lane V = 4 / 4 / 2 or 1, as SEG_DISPATCH of heads.hip).  The target is a label plane (B,H,W) in its own dtype, truncated
-// to an integer as .long() does, or K one-hot planes whose arg-max over the channels of keep_mask is taken here (the first maximum
-// wins; an all-zero pixel gives the first kept channel, as torch.argmax does).  The input holds logits -- the log-softmax over all K
+// (b) class-index cross entropy of (B,K,H,W) fp32 input, 2 <= K <= 8 (KT and V: PLANE_DISPATCH).  The target is a label plane (B,H,W) in its own
+// dtype, truncated to an integer as .long() does, or K one-hot planes whose arg-max over the channels of keep_mask is taken
+// (plane_labels: the first maximum wins).  The input holds logits -- the log-softmax over all K
 // channels is taken here -- or log-probabilities used as they are (log_input).
 // -log p_c = (max - l_c) + log1p(sum of the other e^(l - max)): the difference is exact in fp64 and the sum leaves out the maximum's
 // own 1, so a confident pixel's tiny loss keeps its relative precision (max + log(sum) - l_c in fp32 would leave it with an absolute
-// error of ulp(|l|)); e^(l - max) has the rounding of its fp32 argument given back, as seg_softmax of heads.hip has it.
+// error of ulp(|l|)); e^(l - max) has the rounding of its fp32 argument given back, as seg_softmax (seg_softmax.h) has it.
 // A label outside [0, K) that is not ignore_index is never used as an index (the class is picked by comparison, not by address):
 // that pixel adds NaN to table[0] and gets a zero gradient.
 // ---------------------------------------------------------------------------------------------
-template <int TK> struct IceTarget;
-template <> struct IceTarget<CMU_ICE_LABEL_I64> { typedef int64_t T; static constexpr bool onehot = false; };
-template <> struct IceTarget<CMU_ICE_LABEL_I32> { typedef int32_t T; static constexpr bool onehot = false; };
-template <> struct IceTarget<CMU_ICE_LABEL_U8> { typedef uint8_t T; static constexpr bool onehot = false; };
-template <> struct IceTarget<CMU_ICE_LABEL_F32> { typedef float T; static constexpr bool onehot = false; };
-template <> struct IceTarget<CMU_ICE_LABEL_F64> { typedef double T; static constexpr bool onehot = false; };
-template <> struct IceTarget<CMU_ICE_ONEHOT_F32> { typedef float T; static constexpr bool onehot = true; };
-template <> struct IceTarget<CMU_ICE_ONEHOT_F64> { typedef double T; static constexpr bool onehot = true; };
-
-// first pixel of pixel group g in plane 0 of its image (seg_group_base of heads.hip)
-__device__ static inline int64_t ice_group_base(int64_t g, int64_t gpi, bool small, int K, int64_t HW, int V) {
-    int64_t b, r;
-    if (small) {
-        const unsigned gu = (unsigned)g, bu = gu / (unsigned)gpi;
-        b = bu;
-        r = gu - bu * (unsigned)gpi;
-    } else {
-        b = g / gpi;
-        r = g - b * gpi;
-    }
-    return b * K * HW + r * V;
-}
 // p = softmax(l) in fp32, nlp[c] = -log p_c (see above)
 template <int KT>
 __device__ static inline void ice_log_softmax(const float (&l)[KT], int K, float (&p)[KT], double (&nlp)[KT]) {
@@ -252,41 +210,8 @@ __device__ static inline void ice_log_softmax(const float (&l)[KT], int K, float
             nlp[c] = ((double)m - (double)l[c]) + lg;
         }
 }
-// labels of the V pixels of group g: the label plane's values truncated, or the arg-max over the kept one-hot channels
 template <int KT, int V, int TK>
-__device__ static inline void ice_labels(const typename IceTarget<TK>::T* __restrict__ tgt, int64_t g, int64_t base, int K, int64_t HW,
-                                         unsigned keep_mask, int64_t (&lab)[V]) {
-    typedef typename IceTarget<TK>::T TT;
-    if (IceTarget<TK>::onehot) {
-        int best[V];
-        TT bv[V];
-#pragma unroll
-        for (int v = 0; v < V; ++v) {
-            best[v] = -1;
-            bv[v] = (TT)0;
-        }
-#pragma unroll
-        for (int c = 0; c < KT; ++c)
-            if (c < K && ((keep_mask >> c) & 1u)) {
-                const PwVec<TT, V> yv = *reinterpret_cast<const PwVec<TT, V>*>(tgt + base + c * HW);
-#pragma unroll
-                for (int v = 0; v < V; ++v)
-                    if (best[v] < 0 || yv.v[v] > bv[v]) {
-                        best[v] = c;
-                        bv[v] = yv.v[v];
-                    }
-            }
-#pragma unroll
-        for (int v = 0; v < V; ++v) lab[v] = best[v];
-    } else {
-        const PwVec<TT, V> tv = *reinterpret_cast<const PwVec<TT, V>*>(tgt + g * V);
-#pragma unroll
-        for (int v = 0; v < V; ++v) lab[v] = (int64_t)tv.v[v];
-    }
-}
-
-template <int KT, int V, int TK>
-__global__ __launch_bounds__(256) void ice_fwd_kernel(const float* __restrict__ x, const typename IceTarget<TK>::T* __restrict__ tgt,
+__global__ __launch_bounds__(256) void ice_fwd_kernel(const float* __restrict__ x, const typename PlaneTarget<TK>::T* __restrict__ tgt,
                                                      const float* __restrict__ class_w, double* __restrict__ ws, int K, int64_t HW,
                                                      int64_t ngroups, int log_input, unsigned keep_mask, int64_t ignore_index) {
     __shared__ double red[4];
@@ -296,13 +221,13 @@ __global__ __launch_bounds__(256) void ice_fwd_kernel(const float* __restrict__ 
     const int64_t gpi = HW / V;
     const bool small = ngroups < (int64_t(1) << 31);
     for (int64_t g = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; g < ngroups; g += (int64_t)gridDim.x * blockDim.x) {
-        const int64_t base = ice_group_base(g, gpi, small, K, HW, V);
-        PwVec<float, V> xv[KT];
+        const int64_t base = plane_group_base(g, gpi, small, K, HW, V);
+        PlaneVec<float, V> xv[KT];
 #pragma unroll
         for (int c = 0; c < KT; ++c)
-            if (c < K) xv[c] = *reinterpret_cast<const PwVec<float, V>*>(x + base + c * HW);
+            if (c < K) xv[c] = *reinterpret_cast<const PlaneVec<float, V>*>(x + base + c * HW);
         int64_t lab[V];
-        ice_labels<KT, V, TK>(tgt, g, base, K, HW, keep_mask, lab);
+        plane_labels<KT, V, TK, false>(tgt, g, base, K, HW, keep_mask, lab);
 #pragma unroll
         for (int v = 0; v < V; ++v) {
             const int64_t t = lab[v];
@@ -346,7 +271,7 @@ __global__ __launch_bounds__(256) void ice_fwd_kernel(const float* __restrict__ 
     }
 }
 template <int KT, int V, int TK>
-__global__ __launch_bounds__(256) void ice_bwd_kernel(const float* __restrict__ x, const typename IceTarget<TK>::T* __restrict__ tgt,
+__global__ __launch_bounds__(256) void ice_bwd_kernel(const float* __restrict__ x, const typename PlaneTarget<TK>::T* __restrict__ tgt,
                                                      const float* __restrict__ class_w, const double* __restrict__ g_up,
                                                      float* __restrict__ dx, int K, int64_t HW, int64_t ngroups, int log_input,
                                                      unsigned keep_mask, int64_t ignore_index) {
@@ -361,13 +286,13 @@ __global__ __launch_bounds__(256) void ice_bwd_kernel(const float* __restrict__ 
     const int64_t gpi = HW / V;
     const bool small = ngroups < (int64_t(1) << 31);
     for (int64_t g = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; g < ngroups; g += (int64_t)gridDim.x * blockDim.x) {
-        const int64_t base = ice_group_base(g, gpi, small, K, HW, V);
-        PwVec<float, V> xv[KT], dv[KT];
+        const int64_t base = plane_group_base(g, gpi, small, K, HW, V);
+        PlaneVec<float, V> xv[KT], dv[KT];
 #pragma unroll
         for (int c = 0; c < KT; ++c)
-            if (c < K) xv[c] = *reinterpret_cast<const PwVec<float, V>*>(x + base + c * HW);
+            if (c < K) xv[c] = *reinterpret_cast<const PlaneVec<float, V>*>(x + base + c * HW);
         int64_t lab[V];
-        ice_labels<KT, V, TK>(tgt, g, base, K, HW, keep_mask, lab);
+        plane_labels<KT, V, TK, false>(tgt, g, base, K, HW, keep_mask, lab);
 #pragma unroll
         for (int v = 0; v < V; ++v) {
             const int64_t t = lab[v];
@@ -399,42 +324,22 @@ __global__ __launch_bounds__(256) void ice_bwd_kernel(const float* __restrict__ 
         }
 #pragma unroll
         for (int c = 0; c < KT; ++c)
-            if (c < K) *reinterpret_cast<PwVec<float, V>*>(dx + base + c * HW) = dv[c];
+            if (c < K) *reinterpret_cast<PlaneVec<float, V>*>(dx + base + c * HW) = dv[c];
     }
 }
 
 template <int KT, int V, int TK>
 static void ice_fwd_launch(const float* x, const void* tgt, const float* class_w, double* ws, int K, int64_t HW, int64_t npix, int log_input,
                            unsigned keep_mask, int64_t ignore_index, int grid, hipStream_t st) {
-    hipLaunchKernelGGL((ice_fwd_kernel<KT, V, TK>), dim3(grid), dim3(256), 0, st, x, (const typename IceTarget<TK>::T*)tgt, class_w, ws, K, HW,
+    hipLaunchKernelGGL((ice_fwd_kernel<KT, V, TK>), dim3(grid), dim3(256), 0, st, x, (const typename PlaneTarget<TK>::T*)tgt, class_w, ws, K, HW,
                        npix / V, log_input, keep_mask, ignore_index);
 }
 template <int KT, int V, int TK>
 static void ice_bwd_launch(const float* x, const void* tgt, const float* class_w, const double* g, float* dx, int K, int64_t HW, int64_t npix,
                            int log_input, unsigned keep_mask, int64_t ignore_index, int grid, hipStream_t st) {
-    hipLaunchKernelGGL((ice_bwd_kernel<KT, V, TK>), dim3(grid), dim3(256), 0, st, x, (const typename IceTarget<TK>::T*)tgt, class_w, g, dx, K,
+    hipLaunchKernelGGL((ice_bwd_kernel<KT, V, TK>), dim3(grid), dim3(256), 0, st, x, (const typename PlaneTarget<TK>::T*)tgt, class_w, g, dx, K,
                        HW, npix / V, log_input, keep_mask, ignore_index);
 }
-// FN<KT, V, TK>(args...) for the runtime class count, vector width and target kind
-#define ICE_DISPATCH_TK(FN, KT, V, tk, ...)                                                    \
-    do {                                                                                       \
-        switch (tk) {                                                                          \
-            case CMU_ICE_LABEL_I64: FN<KT, V, CMU_ICE_LABEL_I64>(__VA_ARGS__); break;          \
-            case CMU_ICE_LABEL_I32: FN<KT, V, CMU_ICE_LABEL_I32>(__VA_ARGS__); break;          \
-            case CMU_ICE_LABEL_U8: FN<KT, V, CMU_ICE_LABEL_U8>(__VA_ARGS__); break;            \
-            case CMU_ICE_LABEL_F32: FN<KT, V, CMU_ICE_LABEL_F32>(__VA_ARGS__); break;          \
-            case CMU_ICE_LABEL_F64: FN<KT, V, CMU_ICE_LABEL_F64>(__VA_ARGS__); break;          \
-            case CMU_ICE_ONEHOT_F32: FN<KT, V, CMU_ICE_ONEHOT_F32>(__VA_ARGS__); break;        \
-            default: FN<KT, V, CMU_ICE_ONEHOT_F64>(__VA_ARGS__);                               \
-        }                                                                                      \
-    } while (0)
-#define ICE_DISPATCH(FN, K, vec, tk, ...)                                                                                          \
-    do {                                                                                                                           \
-        if ((K) <= 2)      { if (vec) ICE_DISPATCH_TK(FN, 2, 4, tk, __VA_ARGS__); else ICE_DISPATCH_TK(FN, 2, 1, tk, __VA_ARGS__); } \
-        else if ((K) <= 4) { if (vec) ICE_DISPATCH_TK(FN, 4, 4, tk, __VA_ARGS__); else ICE_DISPATCH_TK(FN, 4, 1, tk, __VA_ARGS__); } \
-        else               { if (vec) ICE_DISPATCH_TK(FN, 8, 2, tk, __VA_ARGS__); else ICE_DISPATCH_TK(FN, 8, 1, tk, __VA_ARGS__); } \
-    } while (0)
-
 static int ice_check(const char* who, const void* x, const void* tgt, int target_kind, int keep_mask, int B, int K, int H, int W) {
     CMU_CHECK_ARG(x && tgt && B > 0 && H > 0 && W > 0, "%s: bad args", who);
     CMU_CHECK_ARG(K >= 2 && K <= PWL_MAX_C, "%s: 2 <= K <= %d classes (got %d)", who, PWL_MAX_C, K);
@@ -442,25 +347,17 @@ static int ice_check(const char* who, const void* x, const void* tgt, int target
     CMU_CHECK_ARG(keep_mask > 0 && keep_mask < (1 << K), "%s: keep_mask 0x%x names no channel, or one past K = %d", who, keep_mask, K);
     return CMU_OK;
 }
-// pixels per lane: 4 (2 at KT = 8) on whole 16-byte chunks of every plane with 16-byte aligned pointers, else 1
-static inline int ice_width(int KT, int64_t HW, const void* a, const void* b, const void* c) {
-    const int V = KT == 8 ? 2 : 4;
-    return (HW % V == 0 && cmu_aligned16(a) && cmu_aligned16(b) && (c == nullptr || cmu_aligned16(c))) ? V : 1;
-}
 extern "C" int64_t cmu_index_ce_ws_bytes(void) { return (int64_t)CE_MAX_BLOCKS * 3 * (int64_t)sizeof(double); }
 extern "C" int cmu_index_ce_fwd(const float* x, const void* target, int target_kind, int log_input, int keep_mask, const float* class_w,
                                 int64_t ignore_index, double* table, int B, int K, int H, int W, void* ws, void* stream) {
     if (int rc = ice_check("cmu_index_ce_fwd", x, target, target_kind, keep_mask, B, K, H, W)) return rc;
     CMU_CHECK_ARG(table && ws, "cmu_index_ce_fwd: bad args");
     hipStream_t st = (hipStream_t)stream;
-    const int64_t HW = (int64_t)H * W, npix = (int64_t)B * HW;
-    const int KT = K <= 2 ? 2 : K <= 4 ? 4 : 8;
-    const int V = ice_width(KT, HW, x, target, nullptr);
-    const int grid = pw_grid(npix / V);
-    ICE_DISPATCH(ice_fwd_launch, K, V > 1, target_kind, x, target, class_w, (double*)ws, K, HW, npix, log_input != 0, (unsigned)keep_mask,
-                 ignore_index, grid, st);
+    const PlaneStream ps = plane_stream(B, K, H, W, x, target, nullptr, nullptr);
+    PLANE_DISPATCH(PLANE_DISPATCH_TK, K, ps.V > 1, ice_fwd_launch, target_kind, x, target, class_w, (double*)ws, K, ps.HW, ps.npix,
+                   log_input != 0, (unsigned)keep_mask, ignore_index, ps.grid, st);
     CMU_CHECK_LAUNCH("cmu_index_ce_fwd");
-    hipLaunchKernelGGL(pw_final_kernel, dim3(3), dim3(64), 0, st, (const double*)ws, grid, table);
+    hipLaunchKernelGGL(plane_final_kernel<false>, dim3(3), dim3(64), 0, st, (const double*)ws, ps.grid, PLANE_ALL_COLUMNS, 1.0, table);
     CMU_CHECK_LAUNCH("cmu_index_ce_fwd(final)");
     return CMU_OK;
 }
@@ -469,12 +366,9 @@ extern "C" int cmu_index_ce_bwd(const float* x, const void* target, int target_k
     if (int rc = ice_check("cmu_index_ce_bwd", x, target, target_kind, keep_mask, B, K, H, W)) return rc;
     CMU_CHECK_ARG(dx, "cmu_index_ce_bwd: bad args");
     hipStream_t st = (hipStream_t)stream;
-    const int64_t HW = (int64_t)H * W, npix = (int64_t)B * HW;
-    const int KT = K <= 2 ? 2 : K <= 4 ? 4 : 8;
-    const int V = ice_width(KT, HW, x, target, dx);
-    const int grid = pw_grid(npix / V);
-    ICE_DISPATCH(ice_bwd_launch, K, V > 1, target_kind, x, target, class_w, g, dx, K, HW, npix, log_input != 0, (unsigned)keep_mask,
-                 ignore_index, grid, st);
+    const PlaneStream ps = plane_stream(B, K, H, W, x, target, dx, nullptr);
+    PLANE_DISPATCH(PLANE_DISPATCH_TK, K, ps.V > 1, ice_bwd_launch, target_kind, x, target, class_w, g, dx, K, ps.HW, ps.npix, log_input != 0,
+                   (unsigned)keep_mask, ignore_index, ps.grid, st);
     CMU_CHECK_LAUNCH("cmu_index_ce_bwd");
     return CMU_OK;
 }

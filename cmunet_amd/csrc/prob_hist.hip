@@ -12,6 +12,7 @@
 #include "common.h"
 #include "head_math.h"
 #include "hist_curves.h"
+#include "plane_stream.h"
 #include "seg_softmax.h"
 
 constexpr int PH_MAX_K = 8;
@@ -28,11 +29,6 @@ constexpr int PH_LDS_TAIL = 64;
 #ifndef PH_AGGREGATE
 #define PH_AGGREGATE 1
 #endif
-
-template <typename T, int V>
-struct alignas(sizeof(T) * V < 16 ? sizeof(T) * V : 16) PhVec {
-    T v[V];
-};
 
 // TY: float / double one-hot planes of src's shape (positive iff y > 0.5) or uint8_t, a (B,H,W) label map (class c positive for row c only;
 // a one-plane src: label != 0).  A lane takes V consecutive pixels of every plane; grid.y = 1 pools all B images into row 0, else grid.y = B
@@ -72,6 +68,7 @@ __global__ __launch_bounds__(PH_THREADS) void prob_hist_kernel(const float* __re
             rq[c] = 0ull;
         }
         for (int64_t g = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; g < ngroups; g += (int64_t)gridDim.x * blockDim.x) {
+            // plane_group_base's split, written out: the image index takes b0 before the multiply, and the label map needs (b, r) too
             int64_t b, r;
             if (small) {
                 const unsigned gu = (unsigned)g, bu = gu / (unsigned)gpi;
@@ -83,15 +80,15 @@ __global__ __launch_bounds__(PH_THREADS) void prob_hist_kernel(const float* __re
             }
             b += b0;
             const int64_t base = b * K * HW + r * V;
-            PhVec<float, V> lv[KT];
-            PhVec<TY, V> yv[LABELS ? 1 : KT];
+            PlaneVec<float, V> lv[KT];
+            PlaneVec<TY, V> yv[LABELS ? 1 : KT];
 #pragma unroll
             for (int c = 0; c < KT; ++c)
                 if (c < K) {
-                    lv[c] = *reinterpret_cast<const PhVec<float, V>*>(src + base + c * HW);
-                    if (!LABELS) yv[LABELS ? 0 : c] = *reinterpret_cast<const PhVec<TY, V>*>(tgt + base + c * HW);
+                    lv[c] = *reinterpret_cast<const PlaneVec<float, V>*>(src + base + c * HW);
+                    if (!LABELS) yv[LABELS ? 0 : c] = *reinterpret_cast<const PlaneVec<TY, V>*>(tgt + base + c * HW);
                 }
-            if (LABELS) yv[0] = *reinterpret_cast<const PhVec<TY, V>*>(tgt + b * HW + r * V);
+            if (LABELS) yv[0] = *reinterpret_cast<const PlaneVec<TY, V>*>(tgt + b * HW + r * V);
 #pragma unroll
             for (int v = 0; v < V; ++v) {
                 float l[KT], p[KT], lse;
@@ -167,18 +164,12 @@ static void prob_hist_launch(const float* src, const void* tgt, int from_logits,
     hipLaunchKernelGGL((prob_hist_kernel<KT, V, TY>), grid, dim3(PH_THREADS), lds, st, src, (const TY*)tgt, from_logits,
                        (unsigned long long*)counts, (unsigned long long*)conf, invalid, K, NB, G, HW, ngroups);
 }
-// FN<KT, V, TY>(args...) for the runtime plane count, vector width and target kind (0 fp32 planes, 1 fp64 planes, 2 uint8 labels)
+// an INNER of PLANE_DISPATCH: the launch for the runtime target kind (0 fp32 planes, 1 fp64 planes, 2 uint8 labels)
 #define PH_DISPATCH_TY(KT, V, kind, ...)                                          \
     do {                                                                          \
         if ((kind) == 0) prob_hist_launch<KT, V, float>(__VA_ARGS__);             \
         else if ((kind) == 1) prob_hist_launch<KT, V, double>(__VA_ARGS__);       \
         else prob_hist_launch<KT, V, uint8_t>(__VA_ARGS__);                       \
-    } while (0)
-#define PH_DISPATCH(K, vec, kind, ...)                                                                         \
-    do {                                                                                                       \
-        if ((K) <= 2) { if (vec) PH_DISPATCH_TY(2, 4, kind, __VA_ARGS__); else PH_DISPATCH_TY(2, 1, kind, __VA_ARGS__); }      \
-        else if ((K) <= 4) { if (vec) PH_DISPATCH_TY(4, 4, kind, __VA_ARGS__); else PH_DISPATCH_TY(4, 1, kind, __VA_ARGS__); } \
-        else { if (vec) PH_DISPATCH_TY(8, 2, kind, __VA_ARGS__); else PH_DISPATCH_TY(8, 1, kind, __VA_ARGS__); }               \
     } while (0)
 
 static inline bool ph_pow2_bins(int NB) { return NB >= 2 && NB <= HC_MAX_BINS && (NB & (NB - 1)) == 0; }
@@ -194,7 +185,8 @@ extern "C" int cmu_prob_hist(const float* src, int from_logits, const void* targ
     CMU_CHECK_ARG(pooled || B <= 65535, "cmu_prob_hist: at most 65535 images with per-image rows (got %d)", B);
     hipStream_t st = (hipStream_t)stream;
     const int64_t HW = (int64_t)H * W;
-    const int KT = K <= 2 ? 2 : K <= 4 ? 4 : 8, VV = KT == 8 ? 2 : 4;
+    // plane_width's rule, but a uint8 label map is aligned to its own V bytes, not 16
+    const int VV = K > 4 ? 2 : 4;
     const size_t talign = target_kind == 2 ? (size_t)VV : 16;
     const bool vec = HW % VV == 0 && cmu_aligned16(src) && reinterpret_cast<uintptr_t>(target) % talign == 0;
     const int V = vec ? VV : 1;
@@ -221,7 +213,7 @@ extern "C" int cmu_prob_hist(const float* src, int from_logits, const void* targ
         }
     }
     const dim3 grid((unsigned)gx, (unsigned)Bout);
-    PH_DISPATCH(K, vec, target_kind, src, target, from_logits, counts, conf, invalid, K, NB, G, HW, ngroups, grid, lds, st);
+    PLANE_DISPATCH(PH_DISPATCH_TY, K, vec, target_kind, src, target, from_logits, counts, conf, invalid, K, NB, G, HW, ngroups, grid, lds, st);
     CMU_CHECK_LAUNCH("cmu_prob_hist");
     return CMU_OK;
 }

@@ -31,7 +31,7 @@ U = 2.0 ** -24
 DEV = "cuda"
 C_GRAD = 16                              # see the module docstring; the issue's ceiling for it
 SHAPES = {"odd": (2, 9, 13), "vec": (3, 64, 64), "issue_large": (5, 256, 256), "scalar_stride": (5, 257, 257), "vec4_stride": (5, 464, 464),
-          "vec2_stride": (5, 328, 328)}
+          "vec2_stride": (5, 328, 328), "misaligned": (3, 8, 8)}
 THRESHOLD = {2: 0.5, 3: 0.3, 5: 0.5, 8: 0.3}
 # The grid is capped at 1,024 blocks of 256 lanes, and a lane takes 4 pixels (K <= 4), 2 (K > 4) or 1 (H*W not a multiple of that):
 # a lane runs its grid-stride loop a second time past 1,048,576 / 524,288 / 262,144 pixels.  The issue's (5,3,256,256) takes the
@@ -268,14 +268,69 @@ def test_loss_and_metric_objects_three_classes(ops, monkeypatch):
 
 def test_stride_cases_pass_their_grid_cap():
     """The arithmetic behind the *_stride cases: more pixel groups than 1,024 blocks of 256 lanes on the path each one takes.
-    A guard on the CASE TABLE, not on the library: it restates seg_vectorisable (pixels per lane: 4 at K <= 4, 2 above, 1 when H*W is
-    no multiple of that) and seg_grid (CE_MAX_BLOCKS = 1024 blocks of 256) of csrc/heads.hip -- change those and this with them."""
+    A guard on the CASE TABLE, not on the library: it restates plane_width (pixels per lane: 4 at K <= 4, 2 above, 1 when H*W is
+    no multiple of that) and plane_grid (CE_MAX_BLOCKS = 1024 blocks of 256) of csrc/plane_stream.h -- change those and this with them."""
     for K, shape, _ in CASES:
         B, H, W = SHAPES[shape]
         V = 1 if (H * W) % (2 if K > 4 else 4) else (2 if K > 4 else 4)
         if shape.endswith("_stride"):
             assert B * H * W // V > 1024 * 256, (K, shape)
             assert V == {"scalar_stride": 1, "vec4_stride": 4, "vec2_stride": 2}[shape]
+
+
+def dev_x(x, offset):
+    """x on the device; ``offset``: starting one element past an allocation's (16-byte aligned) start."""
+    if not offset:
+        return x.to(DEV)
+    buf = torch.empty(x.numel() + 1, dtype=x.dtype, device=DEV)
+    buf[1:].copy_(x.reshape(-1))
+    v = buf[1:].view(x.shape)
+    assert v.data_ptr() % 16 == x.element_size() and v.is_contiguous()
+    return v
+
+
+@pytest.mark.parametrize("off", ["logits", "target"])
+@pytest.mark.parametrize("K", [2, 5])
+def test_misaligned_pointers_take_the_one_pixel_path(ops, K, off):
+    """(3,K,8,8): H*W = 64 allows 4 (K = 2) and 2 (K = 5) pixels per lane, so a pointer one element past a 16-byte boundary is all that
+    sends the pass down the one-pixel path (plane_width of csrc/plane_stream.h).  Forward and backward hold the bounds of the ``odd``
+    cases against the same fp64 references.  Element by element the one-pixel path computes what the vector path does: dlogits and
+    spr_hard (a sum of exact 0 / 1) equal the aligned tensors' bit for bit.  The other sums do not have to: a lane adds its
+    four pixels before the block does, so rounded fp64 terms meet in another order -- as for the sum S of the pointwise suite."""
+    from cmunet_amd import _lib
+    (a, b, cc), cfg = MIXES[4]                                # Dice, CE and IoU at once
+    ign = sorted({i % K for i in cfg["ign"]})
+    for target in ("onehot64", "onehot32", "soft64"):
+        c = make_case(K, "misaligned", target)
+        w = c.w.double()
+        g_tp, g_spr = soft_grads(c, a, cc, ign, cfg["beta"], cfg["eps"])
+        tables, grads = [], []
+        for lo_off, y_off in ((0, 0), (off == "logits", off == "target")):
+            ld, yd, wd = dev_x(c.logits, lo_off), dev_x(c.y_dev, y_off), c.w.to(DEV)
+            table = torch.empty(1 + 5 * K, dtype=torch.float64, device=DEV)
+            ws = torch.empty(_lib.lib().cmu_seg_stats_ws_bytes(K), dtype=torch.uint8, device=DEV)
+            ops.seg_stats_fwd(ld, yd, wd, c.thr, table, ws)
+            tables.append(table.cpu())
+            dl = torch.full(c.logits.shape, 7.0, device=DEV)
+            ops.seg_stats_bwd(ld, yd, wd, torch.tensor([b], dtype=torch.float64, device=DEV), g_tp.to(DEV), g_spr.to(DEV), dl)
+            grads.append(dl.cpu())
+        t = tables[1]
+        ce = float(ce_weighted(c.L, c.y, w))
+        ce_bound = 8 * U * float((w.view(1, K, 1, 1) * c.y * (c.L.abs() + c.lse.abs())).sum() / c.npix)
+        print(f"K={K} {off} {target}: ce {float(t[0]):.9g} ref {ce:.9g} err/bound {abs(float(t[0]) - ce) / ce_bound:.3g}")
+        assert abs(float(t[0]) - ce) <= ce_bound
+        for name, got, want, k in (("tp_soft", t[1:1 + K], c.tp_soft, 16), ("spr_soft", t[1 + K:1 + 2 * K], c.spr_soft, 16),
+                                   ("tp_hard", t[1 + 2 * K:1 + 3 * K], c.tp_hard, 2), ("spr_hard", t[1 + 3 * K:1 + 4 * K], c.spr_hard, 2),
+                                   ("sgt", t[1 + 4 * K:], c.sgt, 2)):
+            assert bool(((got - want).abs() <= k * U * want.abs()).all()), (name, got.tolist(), want.tolist())
+        lo = c.L.clone().requires_grad_(True)
+        (a * OL.dice_loss(lo, c.y, eps=cfg["eps"], beta=cfg["beta"], threshold=None, ignore_channels=ign) + b * ce_weighted(lo, c.y, w)
+         + cc * OL.iou_loss(lo, c.y, eps=cfg["eps"], threshold=None, ignore_channels=ign)).backward()
+        bound = grad_bound(c, b, g_tp, g_spr, w)
+        err = (grads[1].double() - lo.grad).abs()
+        print(f"K={K} {off} {target}: dlogits worst err / bound {float((err / bound.clamp_min(1e-300)).max()):.4f}")
+        assert bool((err <= bound).all())
+        assert torch.equal(grads[1], grads[0]) and torch.equal(tables[1][1 + 3 * K:1 + 4 * K], tables[0][1 + 3 * K:1 + 4 * K])
 
 
 def test_criterion_and_metrics_do_not_wait_for_the_device(ops):
