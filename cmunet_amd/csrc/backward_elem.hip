@@ -231,12 +231,8 @@ static int bn_bwd_reduce_t(const void* dA, int64_t ldd, const void* y, int64_t l
 }
 
 static int check_pair(const char* name, const void* a, int64_t lda, const void* b, int64_t ldb, int C, int dt) {
-    const int es = cmu_dtype_size(dt);
-    CMU_CHECK_ARG(es > 0, "%s: bad dtype %d", name, dt);
-    const int epc = 16 / es;
-    CMU_CHECK_ARG(a && b && cmu_aligned16(a) && cmu_aligned16(b), "%s: null / unaligned tensor", name);
-    CMU_CHECK_ARG(C > 0 && C % epc == 0 && lda % epc == 0 && ldb % epc == 0 && lda >= C && ldb >= C, "%s: C=%d / ld alignment (multiple of %d)", name, C, epc);
-    return CMU_OK;
+    const int rc = cmu_check_act(name, a, lda, C, dt);
+    return rc ? rc : cmu_check_act(name, b, ldb, C, dt);
 }
 
 extern "C" int64_t cmu_bn_bwd_ws_bytes(int C) { return BNWS_HDR + (int64_t)RED_MAX_BLOCKS * 2 * C * (int64_t)sizeof(float); }

@@ -74,6 +74,35 @@ struct CmuPerDevice {
     }
 };
 
+// Launch of a kernel that asks for more dynamic LDS than the 64 KB a function gets by default: raise the function's limit once per device, then
+// launch.  The kernel's ADDRESS is the template argument, so every instantiation of a kernel template has a flag of its own (a flag keyed on
+// the function type would be shared by all kernels with one signature, and the second of them would launch without its limit).  lds_bytes is
+// a constant of the instantiation.  The caller sets its kernel tag and runs CMU_CHECK_LAUNCH after a CMU_OK.
+template <auto Kernel, class... Args>
+static int cmu_launch_lds(dim3 grid, dim3 block, int lds_bytes, hipStream_t st, const char* name, const Args&... args) {
+    static CmuPerDevice attr_set;   // hipFuncSetAttribute is per device
+    if (!attr_set.done()) {
+        hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void*>(Kernel), hipFuncAttributeMaxDynamicSharedMemorySize, lds_bytes);
+        if (e != hipSuccess) {
+            cmu_set_error("%s: hipFuncSetAttribute(%d B LDS): %s", name, lds_bytes, hipGetErrorString(e));
+            return CMU_ERR_LAUNCH;
+        }
+        attr_set.mark();
+    }
+    hipLaunchKernelGGL(Kernel, grid, block, lds_bytes, st, args...);
+    return CMU_OK;
+}
+
+// An NHWC activation view of C channels with pixel stride ld: a known dtype, a 16-byte aligned base, and C and ld in whole 16-byte chunks
+static inline int cmu_check_act(const char* name, const void* ptr, int64_t ld, int C, int dt) {
+    const int es = cmu_dtype_size(dt);
+    CMU_CHECK_ARG(es > 0, "%s: bad dtype %d", name, dt);
+    const int epc = 16 / es;
+    CMU_CHECK_ARG(ptr && cmu_aligned16(ptr) && C > 0 && C % epc == 0 && ld % epc == 0 && ld >= C,
+                  "%s: null / unaligned tensor, or C=%d, ld=%lld not multiples of the %d-element chunk with ld >= C", name, C, (long long)ld, epc);
+    return CMU_OK;
+}
+
 // device-resident state of the dynamic loss scaler (cmu_amp_*; 32 bytes, see include/cmunet_hip.h)
 struct CmuAmpState {
     float scale;          // current loss scale

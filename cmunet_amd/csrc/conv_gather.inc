@@ -249,22 +249,13 @@ __global__ __launch_bounds__(512) void conv_gather_kernel(const IGParams p) {
 template <class TR, int NB>
 static int launch_conv_gather_nb(IGParams p, int64_t max_rows, hipStream_t st) {
     typedef CGCfg<TR> C;
-    static CmuPerDevice attr_set;   // hipFuncSetAttribute is per device
     constexpr int LDS = C::MAIN_BYTES + 1024 > IG3Cfg<TR, NB, 1>::EPI_STAGE + 1024 ? C::MAIN_BYTES + 1024 : IG3Cfg<TR, NB, 1>::EPI_STAGE + 1024;
     static_assert(LDS <= 163840, "LDS budget");
-    if (!attr_set.done()) {
-        hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void*>(&conv_gather_kernel<TR, NB>), hipFuncAttributeMaxDynamicSharedMemorySize, LDS);
-        if (e != hipSuccess) {
-            cmu_set_error("cmu_conv3x3_fwd_rows: hipFuncSetAttribute(%d B LDS): %s", LDS, hipGetErrorString(e));
-            return CMU_ERR_LAUNCH;
-        }
-        attr_set.mark();
-    }
     p.nblk = p.N / NB;
     p.npad = cmu_conv3x3_npad(p.N);
     p.nslices32 = p.K / (32 / C::ES);
     p.total_blocks = cmu_div_up64(max_rows, 256) * p.nblk;
-    hipLaunchKernelGGL((conv_gather_kernel<TR, NB>), dim3((unsigned)p.total_blocks), dim3(512), LDS, st, p);
+    if (int rc = cmu_launch_lds<&conv_gather_kernel<TR, NB>>(dim3((unsigned)p.total_blocks), dim3(512), LDS, st, "cmu_conv3x3_fwd_rows", p)) return rc;
     cmu_set_kernel_tag("conv_gather_kernel");
     CMU_CHECK_LAUNCH("cmu_conv3x3_fwd_rows");
     return CMU_OK;

@@ -249,22 +249,12 @@ __global__ __launch_bounds__(512) void conv_gemm_kernel(const IGParams p) {
 template <class TR, bool DG, bool TF>
 static int launch_conv_gemm(IGParams p, hipStream_t st, const char* name) {
     typedef CGCfg<TR> C;
-    static CmuPerDevice attr_set;   // hipFuncSetAttribute is per device
-    if (!attr_set.done()) {
-        hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void*>(&conv_gemm_kernel<TR, DG, TF>),
-                                           hipFuncAttributeMaxDynamicSharedMemorySize, C::LDS_BYTES);
-        if (e != hipSuccess) {
-            cmu_set_error("%s(gemm): hipFuncSetAttribute(%d B LDS): %s", name, C::LDS_BYTES, hipGetErrorString(e));
-            return CMU_ERR_LAUNCH;
-        }
-        attr_set.mark();
-    }
     p.tilesX = cmu_div_up(p.W, 16);
     p.tilesY = cmu_div_up(p.H, 16);
     p.nblk = p.N / C::NB;
     p.npad = cmu_div_up(p.N, 64) * 64;
     p.total_blocks = (int64_t)p.B * p.tilesX * p.tilesY * p.nblk;
-    hipLaunchKernelGGL((conv_gemm_kernel<TR, DG, TF>), dim3((unsigned)p.total_blocks), dim3(512), C::LDS_BYTES, st, p);
+    if (int rc = cmu_launch_lds<&conv_gemm_kernel<TR, DG, TF>>(dim3((unsigned)p.total_blocks), dim3(512), C::LDS_BYTES, st, name, p)) return rc;
     cmu_set_kernel_tag("conv_gemm_kernel");
     CMU_CHECK_LAUNCH(name);
     return CMU_OK;
@@ -446,22 +436,12 @@ template <class TR, bool DG, bool TF>
 static int launch_conv_gemm_s(IGParams p, hipStream_t st, const char* name) {
     typedef CGSCfg<TR> C;
     static_assert(2 * C::LDS_BYTES <= 163840, "two workgroups per CU");
-    static CmuPerDevice attr_set;   // hipFuncSetAttribute is per device
-    if (!attr_set.done()) {
-        hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void*>(&conv_gemm_s_kernel<TR, DG, TF>),
-                                           hipFuncAttributeMaxDynamicSharedMemorySize, C::LDS_BYTES);
-        if (e != hipSuccess) {
-            cmu_set_error("%s(gemm, shallow K): hipFuncSetAttribute(%d B LDS): %s", name, C::LDS_BYTES, hipGetErrorString(e));
-            return CMU_ERR_LAUNCH;
-        }
-        attr_set.mark();
-    }
     p.tilesX = cmu_div_up(p.W, 16);
     p.tilesY = cmu_div_up(p.H, 16);
     p.nblk = p.N / C::NB;
     p.npad = cmu_div_up(p.N, 64) * 64;
     p.total_blocks = (int64_t)p.B * p.tilesX * p.tilesY * p.nblk;
-    hipLaunchKernelGGL((conv_gemm_s_kernel<TR, DG, TF>), dim3((unsigned)p.total_blocks), dim3(512), C::LDS_BYTES, st, p);
+    if (int rc = cmu_launch_lds<&conv_gemm_s_kernel<TR, DG, TF>>(dim3((unsigned)p.total_blocks), dim3(512), C::LDS_BYTES, st, name, p)) return rc;
     cmu_set_kernel_tag("conv_gemm_s_kernel");
     CMU_CHECK_LAUNCH(name);
     return CMU_OK;

@@ -549,28 +549,9 @@ __global__ __launch_bounds__(256, 2) void conv_igemm_kernel(const IGParams p) {
 template <class TR, int MODE>
 static int launch_igemm(const IGParams& p, hipStream_t st, const char* name) {
     typedef IGCfg<TR, MODE> C;
-    static CmuPerDevice attr_set;   // hipFuncSetAttribute is per device
-    if (!attr_set.done()) {
-        hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void*>(&conv_igemm_kernel<TR, MODE>),
-                                           hipFuncAttributeMaxDynamicSharedMemorySize, C::LDS_BYTES);
-        if (e != hipSuccess) {
-            cmu_set_error("%s: hipFuncSetAttribute(%d B LDS): %s", name, C::LDS_BYTES, hipGetErrorString(e));
-            return CMU_ERR_LAUNCH;
-        }
-        attr_set.mark();
-    }
-    hipLaunchKernelGGL((conv_igemm_kernel<TR, MODE>), dim3((unsigned)p.total_blocks), dim3(256), C::LDS_BYTES, st, p);
+    if (int rc = cmu_launch_lds<&conv_igemm_kernel<TR, MODE>>(dim3((unsigned)p.total_blocks), dim3(256), C::LDS_BYTES, st, name, p)) return rc;
     cmu_set_kernel_tag("conv_igemm_kernel");
     CMU_CHECK_LAUNCH(name);
-    return CMU_OK;
-}
-
-static int check_act(const char* name, const void* ptr, int64_t ld, int C, int dt) {
-    const int epc = 16 / cmu_dtype_size(dt);
-    CMU_CHECK_ARG(ptr != nullptr, "%s: null tensor", name);
-    CMU_CHECK_ARG(cmu_aligned16(ptr), "%s: tensor not 16-byte aligned", name);
-    CMU_CHECK_ARG(ld >= C && ld % epc == 0, "%s: pixel stride %lld must be >= C=%d and a multiple of %d", name, (long long)ld, C, epc);
-    CMU_CHECK_ARG(C % epc == 0, "%s: channels %d must be a multiple of %d", name, C, epc);
     return CMU_OK;
 }
 
@@ -625,8 +606,8 @@ extern "C" int cmu_conv3x3_fwd(const void* x, int64_t ldx, const float* in_scale
     CMU_CHECK_ARG(B > 0 && H > 0 && W > 0 && Cin > 0 && Cout > 0, "cmu_conv3x3_fwd: bad dims");
     CMU_CHECK_ARG(cmu_dtype_size(dt) > 0, "cmu_conv3x3_fwd: bad dtype %d", dt);
     int rc;
-    if ((rc = check_act("cmu_conv3x3_fwd(x)", x, ldx, Cin, dt))) return rc;
-    if ((rc = check_act("cmu_conv3x3_fwd(y)", y, ldy, Cout, dt))) return rc;
+    if ((rc = cmu_check_act("cmu_conv3x3_fwd(x)", x, ldx, Cin, dt))) return rc;
+    if ((rc = cmu_check_act("cmu_conv3x3_fwd(y)", y, ldy, Cout, dt))) return rc;
     CMU_CHECK_ARG(wpacked && cmu_aligned16(wpacked), "cmu_conv3x3_fwd: packed weights null/unaligned");
     CMU_CHECK_ARG((in_scale == nullptr) == (in_shift == nullptr), "cmu_conv3x3_fwd: scale/shift must both be set");
     CMU_CHECK_ARG(relu_from % (16 / cmu_dtype_size(dt)) == 0, "cmu_conv3x3_fwd: relu_from=%d must be a multiple of the 16-byte chunk", relu_from);
@@ -646,8 +627,8 @@ extern "C" int cmu_convT2x2_fwd(const void* x, int64_t ldx, const float* in_scal
     CMU_CHECK_ARG(B > 0 && H > 0 && W > 0 && Cin > 0 && Cout > 0, "cmu_convT2x2_fwd: bad dims");
     CMU_CHECK_ARG(cmu_dtype_size(dt) > 0, "cmu_convT2x2_fwd: bad dtype %d", dt);
     int rc;
-    if ((rc = check_act("cmu_convT2x2_fwd(x)", x, ldx, Cin, dt))) return rc;
-    if ((rc = check_act("cmu_convT2x2_fwd(out)", out, ldo, Cout, dt))) return rc;
+    if ((rc = cmu_check_act("cmu_convT2x2_fwd(x)", x, ldx, Cin, dt))) return rc;
+    if ((rc = cmu_check_act("cmu_convT2x2_fwd(out)", out, ldo, Cout, dt))) return rc;
     CMU_CHECK_ARG(wpacked && cmu_aligned16(wpacked) && bias, "cmu_convT2x2_fwd: weights/bias null or unaligned");
     CMU_CHECK_ARG((in_scale == nullptr) == (in_shift == nullptr), "cmu_convT2x2_fwd: scale/shift must both be set");
     CMU_CHECK_ARG(relu_from % (16 / cmu_dtype_size(dt)) == 0, "cmu_convT2x2_fwd: relu_from=%d must be a multiple of the 16-byte chunk", relu_from);
@@ -664,8 +645,8 @@ extern "C" int cmu_convT2x2_dgrad(const void* dOut, int64_t ldd, const void* wpa
     CMU_CHECK_ARG(B > 0 && H > 0 && W > 0 && Cin > 0 && Cout > 0, "cmu_convT2x2_dgrad: bad dims");
     CMU_CHECK_ARG(cmu_dtype_size(dt) > 0, "cmu_convT2x2_dgrad: bad dtype %d", dt);
     int rc;
-    if ((rc = check_act("cmu_convT2x2_dgrad(dOut)", dOut, ldd, Cout, dt))) return rc;
-    if ((rc = check_act("cmu_convT2x2_dgrad(dX)", dX, ldx, Cin, dt))) return rc;
+    if ((rc = cmu_check_act("cmu_convT2x2_dgrad(dOut)", dOut, ldd, Cout, dt))) return rc;
+    if ((rc = cmu_check_act("cmu_convT2x2_dgrad(dX)", dX, ldx, Cin, dt))) return rc;
     CMU_CHECK_ARG(wpacked_dgrad && cmu_aligned16(wpacked_dgrad), "cmu_convT2x2_dgrad: packed weights null/unaligned");
     IGParams p = {};
     p.x = dOut; p.ldx = ldd; p.in_scale = nullptr; p.in_shift = nullptr; p.relu_from = 0;
@@ -694,8 +675,8 @@ extern "C" int cmu_conv3x3_fwd_tiles(const void* x, int64_t ldx, const float* in
     CMU_CHECK_ARG(B > 0 && H > 0 && W > 0 && Cin > 0 && Cout > 0 && tile_list && tile_count, "cmu_conv3x3_fwd_tiles: bad dims / null list");
     CMU_CHECK_ARG(cmu_dtype_size(dt) > 0, "cmu_conv3x3_fwd_tiles: bad dtype %d", dt);
     int rc;
-    if ((rc = check_act("cmu_conv3x3_fwd_tiles(x)", x, ldx, Cin, dt))) return rc;
-    if ((rc = check_act("cmu_conv3x3_fwd_tiles(y)", y, ldy, Cout, dt))) return rc;
+    if ((rc = cmu_check_act("cmu_conv3x3_fwd_tiles(x)", x, ldx, Cin, dt))) return rc;
+    if ((rc = cmu_check_act("cmu_conv3x3_fwd_tiles(y)", y, ldy, Cout, dt))) return rc;
     CMU_CHECK_ARG(wpacked && cmu_aligned16(wpacked), "cmu_conv3x3_fwd_tiles: packed weights null/unaligned");
     CMU_CHECK_ARG((in_scale == nullptr) == (in_shift == nullptr), "cmu_conv3x3_fwd_tiles: scale/shift must both be set");
     CMU_CHECK_ARG(relu_from % (16 / cmu_dtype_size(dt)) == 0, "cmu_conv3x3_fwd_tiles: relu_from=%d must be a multiple of the 16-byte chunk", relu_from);
@@ -738,8 +719,8 @@ extern "C" int cmu_conv3x3_fwd_rows(const void* x, int64_t ldx, const void* wpac
     CMU_CHECK_ARG(B > 0 && H > 0 && W > 0 && Cin > 0 && Cout > 0 && rows && n_rows && max_rows > 0, "cmu_conv3x3_fwd_rows: bad dims / null list");
     CMU_CHECK_ARG(cmu_dtype_size(dt) > 0, "cmu_conv3x3_fwd_rows: bad dtype %d", dt);
     int rc;
-    if ((rc = check_act("cmu_conv3x3_fwd_rows(x)", x, ldx, Cin, dt))) return rc;
-    if ((rc = check_act("cmu_conv3x3_fwd_rows(y)", y, ldy, Cout, dt))) return rc;
+    if ((rc = cmu_check_act("cmu_conv3x3_fwd_rows(x)", x, ldx, Cin, dt))) return rc;
+    if ((rc = cmu_check_act("cmu_conv3x3_fwd_rows(y)", y, ldy, Cout, dt))) return rc;
     CMU_CHECK_ARG(wpacked && cmu_aligned16(wpacked), "cmu_conv3x3_fwd_rows: packed weights null/unaligned");
     IGParams p = {};
     p.x = x; p.ldx = ldx; p.w = wpacked; p.y = y; p.ldy = ldy;
@@ -964,7 +945,7 @@ extern "C" int cmu_sparse_tile_list(const uint8_t* active, int f, int B, int H, 
 static int check_bnstats(const char* name, const void* yraw, int64_t ldy, const float* scale, const float* shift, const float* mean,
                          const float* invstd, const float* bstats, int N, int dt) {
     int rc;
-    if ((rc = check_act(name, yraw, ldy, N, dt))) return rc;
+    if ((rc = cmu_check_act(name, yraw, ldy, N, dt))) return rc;
     CMU_CHECK_ARG(scale && shift && mean && invstd && bstats, "%s: null BatchNorm argument", name);
     return CMU_OK;
 }
@@ -975,8 +956,8 @@ extern "C" int cmu_conv3x3_dgrad_bn(const void* dY, int64_t ldd, const void* wpa
     CMU_CHECK_ARG(B > 0 && H > 0 && W > 0 && K > 0 && N > 0, "cmu_conv3x3_dgrad_bn: bad dims");
     CMU_CHECK_ARG(cmu_dtype_size(dt) > 0, "cmu_conv3x3_dgrad_bn: bad dtype %d", dt);
     int rc;
-    if ((rc = check_act("cmu_conv3x3_dgrad_bn(dY)", dY, ldd, K, dt))) return rc;
-    if ((rc = check_act("cmu_conv3x3_dgrad_bn(dX)", dX, ldx, N, dt))) return rc;
+    if ((rc = cmu_check_act("cmu_conv3x3_dgrad_bn(dY)", dY, ldd, K, dt))) return rc;
+    if ((rc = cmu_check_act("cmu_conv3x3_dgrad_bn(dX)", dX, ldx, N, dt))) return rc;
     if ((rc = check_bnstats("cmu_conv3x3_dgrad_bn(yraw)", yraw, ldy, scale, shift, save_mean, save_invstd, bstats, N, dt))) return rc;
     CMU_CHECK_ARG(wpacked_flip && cmu_aligned16(wpacked_flip), "cmu_conv3x3_dgrad_bn: packed weights null/unaligned");
     CMU_CHECK_ARG((int64_t)B * cmu_div_up(H, CMU_TH) * cmu_div_up(W, CMU_TW) * cmu_div_up(N, 64) < (1ll << 31), "cmu_conv3x3_dgrad_bn: grid too large");
@@ -995,8 +976,8 @@ extern "C" int cmu_convT2x2_dgrad_bn(const void* dOut, int64_t ldd, const void* 
     CMU_CHECK_ARG(B > 0 && H > 0 && W > 0 && Cin > 0 && Cout > 0, "cmu_convT2x2_dgrad_bn: bad dims");
     CMU_CHECK_ARG(cmu_dtype_size(dt) > 0, "cmu_convT2x2_dgrad_bn: bad dtype %d", dt);
     int rc;
-    if ((rc = check_act("cmu_convT2x2_dgrad_bn(dOut)", dOut, ldd, Cout, dt))) return rc;
-    if ((rc = check_act("cmu_convT2x2_dgrad_bn(dX)", dX, ldx, Cin, dt))) return rc;
+    if ((rc = cmu_check_act("cmu_convT2x2_dgrad_bn(dOut)", dOut, ldd, Cout, dt))) return rc;
+    if ((rc = cmu_check_act("cmu_convT2x2_dgrad_bn(dX)", dX, ldx, Cin, dt))) return rc;
     if ((rc = check_bnstats("cmu_convT2x2_dgrad_bn(yraw)", yraw, ldy, scale, shift, save_mean, save_invstd, bstats, Cin, dt))) return rc;
     CMU_CHECK_ARG(wpacked_dgrad && cmu_aligned16(wpacked_dgrad), "cmu_convT2x2_dgrad_bn: packed weights null/unaligned");
     IGParams p = {};

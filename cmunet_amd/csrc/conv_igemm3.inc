@@ -559,16 +559,7 @@ __global__ __launch_bounds__(512) void conv_igemm3_kernel(const IGParams p) {
 template <class TR, int NB, bool TF, int TWB>
 static int launch_igemm3_cfg(IGParams p, hipStream_t st) {
     typedef IG3Cfg<TR, NB, TWB> C;
-    static CmuPerDevice attr_set;   // hipFuncSetAttribute is per device
-    if (!attr_set.done()) {
-        hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void*>(&conv_igemm3_kernel<TR, NB, TF, TWB>),
-                                           hipFuncAttributeMaxDynamicSharedMemorySize, C::LDS_BYTES);
-        if (e != hipSuccess) {
-            cmu_set_error("cmu_conv3x3_fwd(wide, 32-byte slices): hipFuncSetAttribute(%d B LDS): %s", C::LDS_BYTES, hipGetErrorString(e));
-            return CMU_ERR_LAUNCH;
-        }
-        attr_set.mark();
-    }
+    constexpr const char* name = "cmu_conv3x3_fwd(wide, 32-byte slices)";
     p.tilesX = cmu_div_up(p.W, C::TW);
     p.tilesY = cmu_div_up(p.H, C::TH);
     p.nblk = p.N / NB;
@@ -576,9 +567,9 @@ static int launch_igemm3_cfg(IGParams p, hipStream_t st) {
     p.nslices = p.nslices32;
     p.npad = cmu_conv3x3_npad(p.N);
     p.total_blocks = (int64_t)p.B * p.tilesX * p.tilesY * p.nblk;
-    hipLaunchKernelGGL((conv_igemm3_kernel<TR, NB, TF, TWB>), dim3((unsigned)p.total_blocks), dim3(512), C::LDS_BYTES, st, p);
+    if (int rc = cmu_launch_lds<&conv_igemm3_kernel<TR, NB, TF, TWB>>(dim3((unsigned)p.total_blocks), dim3(512), C::LDS_BYTES, st, name, p)) return rc;
     cmu_set_kernel_tag("conv_igemm3_kernel");
-    CMU_CHECK_LAUNCH("cmu_conv3x3_fwd(wide, 32-byte slices)");
+    CMU_CHECK_LAUNCH(name);
     return CMU_OK;
 }
 

@@ -708,16 +708,7 @@ static int launch_igemm3p_cfg(IGParams p, hipStream_t st) {
     typedef IG3Cfg<TR, NB, 2, THB> C;
     typedef IG3PCfg<TR, NB, THB, WRES> P;
     static_assert(P::LDS_BYTES <= 163840, "LDS budget");
-    static CmuPerDevice attr_set;   // hipFuncSetAttribute is per device
-    if (!attr_set.done()) {
-        hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void*>(&conv_igemm3p_kernel<TR, NB, TF, BST, THB, WRES, PART>),
-                                           hipFuncAttributeMaxDynamicSharedMemorySize, P::LDS_BYTES);
-        if (e != hipSuccess) {
-            cmu_set_error("cmu_conv3x3_fwd(wide, persistent): hipFuncSetAttribute(%d B LDS): %s", P::LDS_BYTES, hipGetErrorString(e));
-            return CMU_ERR_LAUNCH;
-        }
-        attr_set.mark();
-    }
+    constexpr const char* name = "cmu_conv3x3_fwd(wide, persistent)";
     p.tilesX = cmu_div_up(p.W, C::TW);
     p.tilesY = cmu_div_up(p.H, C::TH);
     p.nblk = p.N / NB;
@@ -733,9 +724,9 @@ static int launch_igemm3p_cfg(IGParams p, hipStream_t st) {
     const int forced = cmu_knob(CMU_KNOB_CONV_PERSIST_GRID);
     const int64_t want = forced > 0 ? forced : cmu_num_cus();
     const int64_t grid = p.total_blocks < want ? p.total_blocks : want;
-    hipLaunchKernelGGL((conv_igemm3p_kernel<TR, NB, TF, BST, THB, WRES, PART>), dim3((unsigned)grid), dim3(512), P::LDS_BYTES, st, p);
+    if (int rc = cmu_launch_lds<&conv_igemm3p_kernel<TR, NB, TF, BST, THB, WRES, PART>>(dim3((unsigned)grid), dim3(512), P::LDS_BYTES, st, name, p)) return rc;
     cmu_set_kernel_tag("conv_igemm3p_kernel");
-    CMU_CHECK_LAUNCH("cmu_conv3x3_fwd(wide, persistent)");
+    CMU_CHECK_LAUNCH(name);
     return CMU_OK;
 }
 

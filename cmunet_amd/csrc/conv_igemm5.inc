@@ -757,16 +757,7 @@ template <class TR, bool TF, bool BST>
 static int launch_igemm5_cfg(IGParams p, hipStream_t st) {
     typedef IG5Cfg C;
     static_assert(C::LDS_BYTES <= 163840 && C::LDS_BYTES_BST <= 163840, "LDS budget");
-    static CmuPerDevice attr_set;
-    if (!attr_set.done()) {
-        hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void*>(&conv_igemm5_kernel<TR, TF, BST>),
-                                           hipFuncAttributeMaxDynamicSharedMemorySize, BST ? C::LDS_BYTES_BST : C::LDS_BYTES);
-        if (e != hipSuccess) {
-            cmu_set_error("cmu_conv3x3_fwd(16x16x32, persistent): hipFuncSetAttribute(%d B LDS): %s", C::LDS_BYTES, hipGetErrorString(e));
-            return CMU_ERR_LAUNCH;
-        }
-        attr_set.mark();
-    }
+    constexpr const char* name = "cmu_conv3x3_fwd(16x16x32, persistent)";
     p.tilesX = p.W / C::TW;
     p.tilesY = p.H / C::TH;
     p.nblk = p.N / C::NB;
@@ -783,9 +774,9 @@ static int launch_igemm5_cfg(IGParams p, hipStream_t st) {
     const int forced = cmu_knob(CMU_KNOB_CONV_PERSIST_GRID);
     const int64_t want = forced > 0 ? forced : cmu_num_cus();
     const int64_t grid = p.total_blocks < want ? p.total_blocks : want;
-    hipLaunchKernelGGL((conv_igemm5_kernel<TR, TF, BST>), dim3((unsigned)grid), dim3(512), BST ? C::LDS_BYTES_BST : C::LDS_BYTES, st, p);
+    if (int rc = cmu_launch_lds<&conv_igemm5_kernel<TR, TF, BST>>(dim3((unsigned)grid), dim3(512), BST ? C::LDS_BYTES_BST : C::LDS_BYTES, st, name, p)) return rc;
     cmu_set_kernel_tag("conv_igemm5_kernel");
-    CMU_CHECK_LAUNCH("cmu_conv3x3_fwd(16x16x32, persistent)");
+    CMU_CHECK_LAUNCH(name);
     return CMU_OK;
 }
 

@@ -478,15 +478,7 @@ template <class TR, bool TF>
 static int launch_igemm6_cfg(IGParams p, hipStream_t st) {
     typedef IG6Cfg C;
     static_assert(C::LDS_BYTES <= 81920, "two workgroups per CU");
-    static CmuPerDevice attr_set;
-    if (!attr_set.done()) {
-        hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void*>(&conv_igemm6_kernel<TR, TF>), hipFuncAttributeMaxDynamicSharedMemorySize, C::LDS_BYTES);
-        if (e != hipSuccess) {
-            cmu_set_error("cmu_conv3x3_fwd(16x16x32, 64-channel items): hipFuncSetAttribute(%d B LDS): %s", C::LDS_BYTES, hipGetErrorString(e));
-            return CMU_ERR_LAUNCH;
-        }
-        attr_set.mark();
-    }
+    constexpr const char* name = "cmu_conv3x3_fwd(16x16x32, 64-channel items)";
     p.tilesX = p.W / C::TW;
     p.tilesY = p.H / C::TH;
     p.nblk = p.N / C::NB;
@@ -500,9 +492,9 @@ static int launch_igemm6_cfg(IGParams p, hipStream_t st) {
     const int forced = cmu_knob(CMU_KNOB_CONV_PERSIST_GRID);
     const int64_t want = forced > 0 ? forced : 2 * cmu_num_cus();
     const int64_t grid = p.total_blocks < want ? p.total_blocks : want;
-    hipLaunchKernelGGL((conv_igemm6_kernel<TR, TF>), dim3((unsigned)grid), dim3(256), C::LDS_BYTES, st, p);
+    if (int rc = cmu_launch_lds<&conv_igemm6_kernel<TR, TF>>(dim3((unsigned)grid), dim3(256), C::LDS_BYTES, st, name, p)) return rc;
     cmu_set_kernel_tag("conv_igemm6_kernel");
-    CMU_CHECK_LAUNCH("cmu_conv3x3_fwd(16x16x32, 64-channel items)");
+    CMU_CHECK_LAUNCH(name);
     return CMU_OK;
 }
 

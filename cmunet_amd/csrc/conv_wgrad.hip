@@ -501,480 +501,306 @@ __global__ __launch_bounds__(256) void channel_sum_final_kernel(const float* __r
 // ---------------------------------------------------------------------------------------------------
 // host side
 // ---------------------------------------------------------------------------------------------------
-static int wg_splitk(int nbase, int ntiles, int mult, int target = 512) {
-    // aim at ~target workgroups (512: two rounds over 256 CUs); every split gets at least one tile
+static int wg_splitk(int nbase, int ntiles, int mult, int target) {
+    // aim at ~target workgroups; every split gets at least one tile
     int s = target / (nbase * mult);
     if (s < 1) s = 1;
     if (s > ntiles) s = ntiles;
     return s;
 }
-// the wide kernels hold one workgroup per CU (LDS): 256 workgroups are exactly one round over the chip, and every
-// workgroup writes its whole accumulator tile to the split-K slab -- half the workgroups is half the slab traffic of
-// the reduction (1.1 ms per bench step at 512).  CMU_WGRAD_BLOCKS overrides (A/B).
-static int cmu_wg_first_target() { return cmu_knob(CMU_KNOB_WGRAD_BLOCKS1); }
-static int cmu_wg_wide_target() { return cmu_knob(CMU_KNOB_WGRAD_BLOCKS); }
-static void wg_geometry(int B, int H, int W, int CA, int CB, int dt, int mult, WGParams& p) {
-    const int CW = 128 / cmu_dtype_size(dt);
-    p.tilesX = cmu_div_up(W, 16);
-    p.tilesY = cmu_div_up(H, 16);
-    p.ntiles = B * p.tilesX * p.tilesY;
-    p.nAB = cmu_div_up(CA, CW);
-    p.nBB = cmu_div_up(CB, CW);
-    p.CApad = p.nAB * CW;
-    p.CBpad = p.nBB * CW;
-    p.splitk = wg_splitk(p.nAB * p.nBB, p.ntiles, mult, mult == 1 ? cmu_wg_first_target() : 512);
-}
 constexpr int CSUM_BLOCKS = 256;
+constexpr int64_t WG_BUF_RANGE = 0x7fff0000ll;   // bytes of one image that a buffer descriptor of the wide kernels can address
 
-// wide-tile kernel (conv_wgrad2.inc): 16-bit dtypes, Cout in whole 128-blocks, Cin in whole 64-blocks.  CMU_WGRAD_WIDE=0 keeps
-// every layer on the first kernel (A/B switch for the benches).
-static bool wg2_shape_ok(int CA, int CB, int dt) {
-    return cmu_knob(CMU_KNOB_WGRAD_WIDE) && cmu_dtype_size(dt) == 2 && CA % 128 == 0 && CB % 64 == 0;
-}
-// swapped roles (conv_wgrad2.inc, SWAP): Cout = 64 with Cin in whole 128-blocks.  CMU_WGRAD_SWAP=0 keeps those layers on the
-// first kernel (A/B switch)
-static bool wg2_swap_ok(int CA, int CB, int dt) {
-    return cmu_knob(CMU_KNOB_WGRAD_SWAP) && cmu_knob(CMU_KNOB_WGRAD_WIDE) && cmu_dtype_size(dt) == 2 && CA == 64 && CB % 128 == 0;
-}
-static void wg2_geometry(int B, int H, int W, int CA, int CB, WGParams& p, bool swap = false) {
-    p.tilesX = cmu_div_up(W, 16);
-    p.tilesY = cmu_div_up(H, 8);
-    p.ntiles = B * p.tilesX * p.tilesY;
-    p.nAB = (swap ? CB : CA) / 128;   // blocks of the plain 128-channel operand
-    p.nBB = (swap ? CA : CB) / 64;    // blocks of the haloed 64-channel operand
-    p.CApad = CA;
-    p.CBpad = CB;
-    p.splitk = wg_splitk(p.nAB * p.nBB, p.ntiles, 1, cmu_wg_wide_target());
-}
-static bool wgT2_shape_ok(int CA, int CB, int dt) {
-    return cmu_knob(CMU_KNOB_WGRAD_WIDE) && cmu_dtype_size(dt) == 2 && CA % 64 == 0 && CB % 128 == 0;
-}
-// 256 X channels per workgroup (conv_wgrad2.inc, NXI = 4) where Cin allows: the deeper decoder levels (CMU_WGT2_NX256=0: A/B)
-static bool wgT2_wide_x(int CB) {
-    return cmu_knob(CMU_KNOB_WGT2_NX256) && CB % 256 == 0;
-}
-static void wgT2_geometry(int B, int H, int W, int CA, int CB, WGParams& p) {
-    p.tilesX = cmu_div_up(W, 16);
-    p.tilesY = cmu_div_up(H, 4);
-    p.ntiles = B * p.tilesX * p.tilesY;
-    p.nAB = CA / 64;
-    p.nBB = CB / (wgT2_wide_x(CB) ? 256 : 128);
-    p.CApad = CA;
-    p.CBpad = CB;
-    p.splitk = wg_splitk(p.nAB * p.nBB, p.ntiles, 1, cmu_wg_wide_target());
-}
-template <class TR, int NXI>
-static int wgradT_wide_launch(const WG2Params& pp, hipStream_t st) {
-    typedef WGT2Cfg<TR, NXI> C;
-    static CmuPerDevice attr_set;   // hipFuncSetAttribute is per device
-    if (!attr_set.done()) {
-        hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void*>(&conv_wgradT2_kernel<TR, NXI>), hipFuncAttributeMaxDynamicSharedMemorySize,
-                                           C::LDS_BYTES);
-        if (e != hipSuccess) {
-            cmu_set_error("cmu_convT2x2_wgrad(wide): hipFuncSetAttribute(%d B LDS): %s", C::LDS_BYTES, hipGetErrorString(e));
-            return CMU_ERR_LAUNCH;
-        }
-        attr_set.mark();
-    }
-    hipLaunchKernelGGL((conv_wgradT2_kernel<TR, NXI>), dim3(pp.g.nAB * pp.g.nBB * pp.g.splitk), dim3(512), C::LDS_BYTES, st, pp);
-    return CMU_OK;
-}
-template <class TR>
-static int wgradT_wide_t(WGParams p, float* dW, float* dbias, hipStream_t st) {
+// splitk decomposed into (tile column, tile row, image) steps for the kernels that walk their K tiles by increments
+static WG2Params wg2_params(const WGParams& p) {
     WG2Params pp;
     pp.g = p;
     pp.dtx = p.splitk % p.tilesX;
     pp.dty = (p.splitk / p.tilesX) % p.tilesY;
     pp.dtb = p.splitk / (p.tilesX * p.tilesY);
-    const int rc = wgT2_wide_x(p.CB) ? wgradT_wide_launch<TR, 4>(pp, st) : wgradT_wide_launch<TR, 2>(pp, st);
-    if (rc != CMU_OK) return rc;
-    cmu_set_kernel_tag("conv_wgradT2_kernel");
-    CMU_CHECK_LAUNCH("cmu_convT2x2_wgrad(wide)");
-    launch_wgrad_reduce((const float*)p.ws, p.splitk, 4, p.CApad, p.CBpad, p.CA, p.CB, dW, 2, st);
-    CMU_CHECK_LAUNCH("cmu_convT2x2_wgrad(reduce)");
-    const float* ws_sum = p.ws + (int64_t)p.splitk * 4 * p.CB * p.CA;
-    hipLaunchKernelGGL(channel_sum_final_kernel, dim3(cmu_div_up(p.CA, 16)), dim3(256), 0, st, ws_sum, p.splitk, p.CA, dbias);
-    CMU_CHECK_LAUNCH("cmu_convT2x2_wgrad(bias final)");
+    return pp;
+}
+
+// One launch function per kernel: the dynamic-LDS launch and the kernel tag (nothing else differs between the forms' launches)
+typedef int (*WGLaunch)(const WGParams& p, hipStream_t st, const char* name);
+template <class TR, int MODE>
+static int wg_launch_first(const WGParams& p, hipStream_t st, const char* name) {
+    const int grid = p.nAB * p.nBB * p.splitk * (MODE == MODE_WT ? 4 : 1);
+    if (int rc = cmu_launch_lds<&conv_wgrad_kernel<TR, MODE>>(dim3(grid), dim3(512), WGCfg<TR, MODE>::LDS_BYTES, st, name, p)) return rc;
+    cmu_set_kernel_tag("conv_wgrad_kernel");
     return CMU_OK;
 }
 template <class TR, bool SWAP>
-static int wgrad3_wide_t(WGParams p, float* dW, hipStream_t st) {
-    typedef WG2Cfg<TR> C;
-    static CmuPerDevice attr_set;   // hipFuncSetAttribute is per device
-    if (!attr_set.done()) {
-        hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void*>(&conv_wgrad2_kernel<TR, SWAP>), hipFuncAttributeMaxDynamicSharedMemorySize,
-                                           C::LDS_BYTES);
-        if (e != hipSuccess) {
-            cmu_set_error("cmu_conv3x3_wgrad(wide): hipFuncSetAttribute(%d B LDS): %s", C::LDS_BYTES, hipGetErrorString(e));
-            return CMU_ERR_LAUNCH;
-        }
-        attr_set.mark();
-    }
-    WG2Params pp;
-    pp.g = p;
-    pp.dtx = p.splitk % p.tilesX;
-    pp.dty = (p.splitk / p.tilesX) % p.tilesY;
-    pp.dtb = p.splitk / (p.tilesX * p.tilesY);
-    hipLaunchKernelGGL((conv_wgrad2_kernel<TR, SWAP>), dim3(p.nAB * p.nBB * p.splitk), dim3(512), C::LDS_BYTES, st, pp);
+static int wg_launch_wide(const WGParams& p, hipStream_t st, const char* name) {
+    if (int rc = cmu_launch_lds<&conv_wgrad2_kernel<TR, SWAP>>(dim3(p.nAB * p.nBB * p.splitk), dim3(512), WG2Cfg<TR>::LDS_BYTES, st, name, wg2_params(p))) return rc;
     cmu_set_kernel_tag("conv_wgrad2_kernel");
-    CMU_CHECK_LAUNCH("cmu_conv3x3_wgrad(wide)");
-    // (the slab is [split][tap][Cout][Cin] in both forms: p.CA = Cout rows of p.CB = Cin)
-    launch_wgrad_reduce((const float*)p.ws, p.splitk, 9, p.CA, p.CB, p.CA, p.CB, dW, (int)MODE_W3, st);
-    CMU_CHECK_LAUNCH("cmu_conv3x3_wgrad(reduce)");
     return CMU_OK;
-}
-
-// 64 n x 64 c form for the 16-bit dtypes (conv_wgrad2s.inc): whole 64-blocks on both sides where neither form above applies (the
-// 64 -> 64 layers).  CMU_WGRAD_SQUARE=0 keeps them on the first kernel (A/B switch: environment read once, cmu_set_dispatch_override in tests).
-static bool wg2s_shape_ok(int CA, int CB, int dt) {
-    return cmu_knob(CMU_KNOB_WGRAD_WIDE) && cmu_knob(CMU_KNOB_WGRAD_SQUARE) && cmu_dtype_size(dt) == 2 && CA % 64 == 0 && CB % 64 == 0 && !wg2_shape_ok(CA, CB, dt) &&
-           !wg2_swap_ok(CA, CB, dt);
-}
-static void wg2s_geometry(int B, int H, int W, int CA, int CB, WGParams& p) {
-    p.tilesX = cmu_div_up(W, 16);
-    p.tilesY = cmu_div_up(H, 8);
-    p.ntiles = B * p.tilesX * p.tilesY;
-    p.nAB = CA / 64;
-    p.nBB = CB / 64;
-    p.CApad = CA;
-    p.CBpad = CB;
-    p.splitk = wg_splitk(p.nAB * p.nBB, p.ntiles, 1, cmu_wg_wide_target());
 }
 template <class TR>
-static int wgrad3_square_t(WGParams p, float* dW, hipStream_t st) {
-    typedef WG2SCfg<TR> C;
-    static CmuPerDevice attr_set;   // hipFuncSetAttribute is per device
-    if (!attr_set.done()) {
-        hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void*>(&conv_wgrad2s_kernel<TR>), hipFuncAttributeMaxDynamicSharedMemorySize,
-                                           C::LDS_BYTES);
-        if (e != hipSuccess) {
-            cmu_set_error("cmu_conv3x3_wgrad(64 x 64): hipFuncSetAttribute(%d B LDS): %s", C::LDS_BYTES, hipGetErrorString(e));
-            return CMU_ERR_LAUNCH;
-        }
-        attr_set.mark();
-    }
-    WG2Params pp;
-    pp.g = p;
-    pp.dtx = p.splitk % p.tilesX;
-    pp.dty = (p.splitk / p.tilesX) % p.tilesY;
-    pp.dtb = p.splitk / (p.tilesX * p.tilesY);
-    hipLaunchKernelGGL((conv_wgrad2s_kernel<TR>), dim3(p.nAB * p.nBB * p.splitk), dim3(512), C::LDS_BYTES, st, pp);
+static int wg_launch_square(const WGParams& p, hipStream_t st, const char* name) {
+    if (int rc = cmu_launch_lds<&conv_wgrad2s_kernel<TR>>(dim3(p.nAB * p.nBB * p.splitk), dim3(512), WG2SCfg<TR>::LDS_BYTES, st, name, wg2_params(p))) return rc;
     cmu_set_kernel_tag("conv_wgrad2s_kernel");
-    CMU_CHECK_LAUNCH("cmu_conv3x3_wgrad(64 x 64)");
-    // (the wave halves wrote separate slabs: 2 x splitk partial sums, summed in slab order)
-    launch_wgrad_reduce((const float*)p.ws, p.splitk * 2, 9, p.CA, p.CB, p.CA, p.CB, dW, (int)MODE_W3, st);
-    CMU_CHECK_LAUNCH("cmu_conv3x3_wgrad(reduce)");
     return CMU_OK;
-}
-
-// fp32 wide kernel (conv_wgrad2f.inc): Cout and Cin in whole 64-blocks (128 n x 64 c blocks when Cout allows, else 64 x 64 with two
-// k-parts).  CMU_WGRAD_WIDE_F32=0 keeps fp32 on the first kernel (A/B switch: environment read once, cmu_set_dispatch_override in tests).
-static bool wg2f_shape_ok(int CA, int CB, int dt) {
-    return cmu_knob(CMU_KNOB_WGRAD_WIDE) && cmu_knob(CMU_KNOB_WGRAD_WIDE_F32) && dt == CMU_F32 && CA % 64 == 0 && CB % 64 == 0;
-}
-static void wg2f_geometry(int B, int H, int W, int CA, int CB, WGParams& p) {
-    p.tilesX = cmu_div_up(W, 16);
-    p.tilesY = cmu_div_up(H, 4);
-    p.ntiles = B * p.tilesX * p.tilesY;
-    p.nAB = CA / (CA % 128 == 0 ? 128 : 64);
-    p.nBB = CB / 64;
-    p.CApad = CA;
-    p.CBpad = CB;
-    p.splitk = wg_splitk(p.nAB * p.nBB, p.ntiles, 1, cmu_wg_wide_target());
 }
 template <int NAI>
-static int wgrad3_wide_f32_t(WGParams p, float* dW, hipStream_t st) {
-    typedef WG2FCfg<NAI> C;
-    static CmuPerDevice attr_set;   // hipFuncSetAttribute is per device
-    if (!attr_set.done()) {
-        hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void*>(&conv_wgrad2f_kernel<NAI>), hipFuncAttributeMaxDynamicSharedMemorySize,
-                                           C::LDS_BYTES);
-        if (e != hipSuccess) {
-            cmu_set_error("cmu_conv3x3_wgrad(wide, fp32): hipFuncSetAttribute(%d B LDS): %s", C::LDS_BYTES, hipGetErrorString(e));
-            return CMU_ERR_LAUNCH;
-        }
-        attr_set.mark();
-    }
-    WG2Params pp;
-    pp.g = p;
-    pp.dtx = p.splitk % p.tilesX;
-    pp.dty = (p.splitk / p.tilesX) % p.tilesY;
-    pp.dtb = p.splitk / (p.tilesX * p.tilesY);
-    hipLaunchKernelGGL((conv_wgrad2f_kernel<NAI>), dim3(p.nAB * p.nBB * p.splitk), dim3(512), C::LDS_BYTES, st, pp);
+static int wg_launch_wide_f32(const WGParams& p, hipStream_t st, const char* name) {
+    if (int rc = cmu_launch_lds<&conv_wgrad2f_kernel<NAI>>(dim3(p.nAB * p.nBB * p.splitk), dim3(512), WG2FCfg<NAI>::LDS_BYTES, st, name, wg2_params(p))) return rc;
     cmu_set_kernel_tag("conv_wgrad2f_kernel");
-    CMU_CHECK_LAUNCH("cmu_conv3x3_wgrad(wide, fp32)");
-    // (the wave halves of the 64 x 64 block wrote separate slabs: KP x splitk partial sums, summed in slab order)
-    launch_wgrad_reduce((const float*)p.ws, p.splitk * C::KP, 9, p.CA, p.CB, p.CA, p.CB, dW, (int)MODE_W3, st);
-    CMU_CHECK_LAUNCH("cmu_conv3x3_wgrad(reduce)");
     return CMU_OK;
 }
-
-template <class TR, int MODE>
-static int launch_wgrad(const WGParams& p, hipStream_t st, const char* name) {
-    typedef WGCfg<TR, MODE> C;
-    static CmuPerDevice attr_set;   // hipFuncSetAttribute is per device
-    if (!attr_set.done()) {
-        hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void*>(&conv_wgrad_kernel<TR, MODE>),
-                                           hipFuncAttributeMaxDynamicSharedMemorySize, C::LDS_BYTES);
-        if (e != hipSuccess) {
-            cmu_set_error("%s: hipFuncSetAttribute(%d B LDS): %s", name, C::LDS_BYTES, hipGetErrorString(e));
-            return CMU_ERR_LAUNCH;
-        }
-        attr_set.mark();
-    }
-    const int grid = p.nAB * p.nBB * p.splitk * (MODE == MODE_WT ? 4 : 1);
-    hipLaunchKernelGGL((conv_wgrad_kernel<TR, MODE>), dim3(grid), dim3(512), C::LDS_BYTES, st, p);
-    cmu_set_kernel_tag("conv_wgrad_kernel");
-    CMU_CHECK_LAUNCH(name);
+template <class TR, int NXI>
+static int wg_launchT_wide(const WGParams& p, hipStream_t st, const char* name) {
+    if (int rc = cmu_launch_lds<&conv_wgradT2_kernel<TR, NXI>>(dim3(p.nAB * p.nBB * p.splitk), dim3(512), WGT2Cfg<TR, NXI>::LDS_BYTES, st, name, wg2_params(p))) return rc;
+    cmu_set_kernel_tag("conv_wgradT2_kernel");
     return CMU_OK;
 }
-template <class TR>
-static int wgrad3_t(WGParams p, float* dW, hipStream_t st) {
-    int rc = launch_wgrad<TR, MODE_W3>(p, st, "cmu_conv3x3_wgrad");
-    if (rc) return rc;
-    launch_wgrad_reduce((const float*)p.ws, p.splitk, 9, p.CApad, p.CBpad, p.CA, p.CB, dW, (int)MODE_W3, st);
-    CMU_CHECK_LAUNCH("cmu_conv3x3_wgrad(reduce)");
-    return CMU_OK;
-}
-template <class TR>
-static int wgradT_t(WGParams p, float* dW, float* dbias, float* ws_sum, hipStream_t st) {
-    int rc = launch_wgrad<TR, MODE_WT>(p, st, "cmu_convT2x2_wgrad");
-    if (rc) return rc;
-    launch_wgrad_reduce((const float*)p.ws, p.splitk, 4, p.CApad, p.CBpad, p.CA, p.CB, dW, (int)MODE_WT, st);
-    CMU_CHECK_LAUNCH("cmu_convT2x2_wgrad(reduce)");
-    // bias gradient: sum of dOut over all (B,2H,2W) pixels
-    const int nchunk = p.CA / TR::EPC;
-    const int cpb = nchunk < 256 ? nchunk : 256, ppb = 256 / cpb, gy = cmu_div_up(nchunk, cpb);
-    const int64_t npix = (int64_t)p.B * 4 * p.H * p.W;
-    int gx = (int)(cmu_div_up64(npix, ppb * 4) < CSUM_BLOCKS ? cmu_div_up64(npix, ppb * 4) : CSUM_BLOCKS);
-    if (gx < 1) gx = 1;
-    hipLaunchKernelGGL((channel_sum_kernel<TR>), dim3(gx, gy), dim3(256), 0, st, (const unsigned char*)p.a, p.lda, ws_sum, npix, p.CA, cpb, ppb);
-    CMU_CHECK_LAUNCH("cmu_convT2x2_wgrad(bias)");
-    hipLaunchKernelGGL(channel_sum_final_kernel, dim3(cmu_div_up(p.CA, 16)), dim3(256), 0, st, (const float*)ws_sum, gx, p.CA, dbias);
-    CMU_CHECK_LAUNCH("cmu_convT2x2_wgrad(bias final)");
-    return CMU_OK;
-}
-
-// fp32 wide ConvTranspose weight gradient (conv_wgrad2f.inc): 128 c x 64 n blocks.  Follows CMU_WGRAD_WIDE_F32.
-static bool wgT2f_shape_ok(int CA, int CB, int dt) { return wg2f_shape_ok(64, 64, dt) && CA % 64 == 0 && CB % 128 == 0; }
-static void wgT2f_geometry(int B, int H, int W, int CA, int CB, WGParams& p) {
-    p.tilesX = cmu_div_up(W, 16);
-    p.tilesY = cmu_div_up(H, 2);
-    p.ntiles = B * p.tilesX * p.tilesY;
-    p.nAB = CA / 64;
-    p.nBB = CB / 128;
-    p.CApad = CA;
-    p.CBpad = CB;
-    p.splitk = wg_splitk(p.nAB * p.nBB, p.ntiles, 1, cmu_wg_wide_target());
-}
-static int wgradT_wide_f32(WGParams p, float* dW, float* dbias, float* ws_sum, hipStream_t st) {
-    typedef WGT2FCfg C;
-    static CmuPerDevice attr_set;   // hipFuncSetAttribute is per device
-    if (!attr_set.done()) {
-        hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void*>(&conv_wgradT2f_kernel), hipFuncAttributeMaxDynamicSharedMemorySize,
-                                           C::LDS_BYTES);
-        if (e != hipSuccess) {
-            cmu_set_error("cmu_convT2x2_wgrad(wide, fp32): hipFuncSetAttribute(%d B LDS): %s", C::LDS_BYTES, hipGetErrorString(e));
-            return CMU_ERR_LAUNCH;
-        }
-        attr_set.mark();
-    }
-    WG2Params pp;
-    pp.g = p;
-    pp.dtx = p.splitk % p.tilesX;
-    pp.dty = (p.splitk / p.tilesX) % p.tilesY;
-    pp.dtb = p.splitk / (p.tilesX * p.tilesY);
-    hipLaunchKernelGGL(conv_wgradT2f_kernel, dim3(p.nAB * p.nBB * p.splitk), dim3(512), C::LDS_BYTES, st, pp);
+static int wg_launchT_wide_f32(const WGParams& p, hipStream_t st, const char* name) {
+    if (int rc = cmu_launch_lds<&conv_wgradT2f_kernel>(dim3(p.nAB * p.nBB * p.splitk), dim3(512), WGT2FCfg::LDS_BYTES, st, name, wg2_params(p))) return rc;
     cmu_set_kernel_tag("conv_wgradT2f_kernel");
-    CMU_CHECK_LAUNCH("cmu_convT2x2_wgrad(wide, fp32)");
-    launch_wgrad_reduce((const float*)p.ws, p.splitk, 4, p.CApad, p.CBpad, p.CA, p.CB, dW, 2, st);
-    CMU_CHECK_LAUNCH("cmu_convT2x2_wgrad(reduce)");
-    // bias gradient: sum of dOut over all (B,2H,2W) pixels (the first path's channel-sum kernels)
-    typedef F32Traits TR;
-    const int nchunk = p.CA / TR::EPC;
-    const int cpb = nchunk < 256 ? nchunk : 256, ppb = 256 / cpb, gy = cmu_div_up(nchunk, cpb);
-    const int64_t npix = (int64_t)p.B * 4 * p.H * p.W;
-    int gx = (int)(cmu_div_up64(npix, ppb * 4) < CSUM_BLOCKS ? cmu_div_up64(npix, ppb * 4) : CSUM_BLOCKS);
-    if (gx < 1) gx = 1;
-    hipLaunchKernelGGL((channel_sum_kernel<TR>), dim3(gx, gy), dim3(256), 0, st, (const unsigned char*)p.a, p.lda, ws_sum, npix, p.CA, cpb, ppb);
-    CMU_CHECK_LAUNCH("cmu_convT2x2_wgrad(bias)");
-    hipLaunchKernelGGL(channel_sum_final_kernel, dim3(cmu_div_up(p.CA, 16)), dim3(256), 0, st, (const float*)ws_sum, gx, p.CA, dbias);
-    CMU_CHECK_LAUNCH("cmu_convT2x2_wgrad(bias final)");
     return CMU_OK;
 }
 
-static int wg_check(const char* name, const void* t, int64_t ld, int C, int dt) {
-    const int es = cmu_dtype_size(dt);
-    CMU_CHECK_ARG(es > 0, "%s: bad dtype %d", name, dt);
-    const int epc = 16 / es;
-    CMU_CHECK_ARG(t && cmu_aligned16(t), "%s: null / unaligned tensor", name);
-    CMU_CHECK_ARG(C > 0 && C % epc == 0 && ld % epc == 0 && ld >= C, "%s: C=%d / ld=%lld must be multiples of %d", name, C, (long long)ld, epc);
-    return CMU_OK;
-}
+// ---- the forms: which kernel serves a shape, with what split-K geometry, and what it writes to the workspace.  One row each; every entry
+// point below -- both size queries, the tile-height query and the three launches -- reads this table through wg_plan / wg_ws_bytes.
+enum WGRange {
+    WG_ANY,      // the first kernel: 64-bit addresses, every shape
+    WG_HALO_B,   // buffer descriptors per image: dY plain, X with its halo row (W + 1 pixels past the image)
+    WG_HALO_A,   // the swapped roles: the halo is on dY, the plain images are X
+    WG_PLAIN     // ConvTranspose: dOut (four pixels per pixel of X) and X without halo
+};
+enum WGBias {
+    WG_BIAS_NONE,
+    WG_BIAS_SUMS,     // the channel-sum kernels run behind the reduction: CSUM_BLOCKS rows of partial sums behind the slabs
+    WG_BIAS_SPLITS    // the kernel wrote one row of partial sums per split behind the slabs: only the final sum runs
+};
+struct WGForm {
+    const char* name;        // of the launch in error messages
+    int family;              // MODE_W3 / MODE_WT
+    int tile_h;              // rows of a K tile (16 pixels wide)
+    int a_blk, b_blk;        // channels of Cout / Cin per workgroup; 0: 128 bytes' worth, and the slab pads the channel count to whole blocks
+    bool swap;               // nAB counts the blocks of Cin and nBB those of Cout
+    int slabs;               // slabs per split (the wave halves of a 64 x 64 block write separate slabs, summed in slab order)
+    int wgs;                 // workgroups per block pair and split (the first ConvTranspose kernel: one per sub-pixel)
+    int aim;                 // knob that holds the number of workgroups the split count aims at; -1: 512 (two rounds over 256 CUs)
+    bool (*shape)(int CA, int CB, int dt);
+    bool (*knobs)(int CA, int CB);
+    bool size_any_knobs;     // the size query counts the form whatever its knobs say
+    WGRange range;
+    int tf_align;            // mask the addresses of a pending transform's scale / shift must clear
+    bool lists8;             // walks 8 x 16 tile lists (cmu_conv3x3_wgrad_tiles)
+    int reduce_mode;         // of launch_wgrad_reduce: MODE_W3, MODE_WT, 2 (slabs [split][ij][c][n])
+    WGBias bias;
+    WGLaunch launch[3];      // by dtype
+};
+static bool wg_on(int, int) { return true; }
+static bool wg_wide_on(int, int) { return cmu_knob(CMU_KNOB_WGRAD_WIDE); }   // CMU_WGRAD_WIDE=0 keeps every layer on the first kernel (A/B switch for the benches)
+static bool wg_wide_f32_on(int, int) { return cmu_knob(CMU_KNOB_WGRAD_WIDE) && cmu_knob(CMU_KNOB_WGRAD_WIDE_F32); }
+static bool wg_nx256(int CB) { return cmu_knob(CMU_KNOB_WGT2_NX256) && CB % 256 == 0; }
+// The wide kernels hold one workgroup per CU (LDS): 256 workgroups (CMU_WGRAD_BLOCKS) are exactly one round over the chip, and every
+// workgroup writes its whole accumulator tile to the split-K slab -- half the workgroups is half the slab traffic of the reduction
+// (1.1 ms per bench step at 512).  The rows of a family stand in the order in which they are tried.
+static const WGForm WG_FORMS[] = {
+    // each row:  name, family, tile_h, a_blk, b_blk, swap, slabs, wgs, aim,
+    //            shape, knobs, size_any_knobs,
+    //            range, tf_align, lists8, reduce_mode, bias, launch by dtype
+    // wide-tile kernel (conv_wgrad2.inc): 16-bit dtypes, Cout in whole 128-blocks, Cin in whole 64-blocks
+    {"cmu_conv3x3_wgrad(wide)", MODE_W3, 8, 128, 64, false, 1, 1, CMU_KNOB_WGRAD_BLOCKS,
+     [](int CA, int CB, int dt) { return cmu_dtype_size(dt) == 2 && CA % 128 == 0 && CB % 64 == 0; }, wg_wide_on, false,
+     WG_HALO_B, 3, true, MODE_W3, WG_BIAS_NONE, {nullptr, wg_launch_wide<F16Traits, false>, wg_launch_wide<BF16Traits, false>}},
+    // swapped roles (conv_wgrad2.inc, SWAP): Cout = 64 with Cin in whole 128-blocks.  CMU_WGRAD_SWAP=0 keeps those layers off it (A/B switch).
+    // (the slab is [split][tap][Cout][Cin] in both forms)
+    {"cmu_conv3x3_wgrad(wide)", MODE_W3, 8, 64, 128, true, 1, 1, CMU_KNOB_WGRAD_BLOCKS,
+     [](int CA, int CB, int dt) { return cmu_dtype_size(dt) == 2 && CA == 64 && CB % 128 == 0; },
+     [](int, int) { return cmu_knob(CMU_KNOB_WGRAD_SWAP) && cmu_knob(CMU_KNOB_WGRAD_WIDE); }, false,
+     WG_HALO_A, 15, false, MODE_W3, WG_BIAS_NONE, {nullptr, wg_launch_wide<F16Traits, true>, wg_launch_wide<BF16Traits, true>}},
+    // 64 n x 64 c form for the 16-bit dtypes (conv_wgrad2s.inc): whole 64-blocks on both sides where neither form above claims the shape
+    // (the 64 -> 64 layers).  CMU_WGRAD_SQUARE=0 keeps them on the first kernel (A/B switch).
+    {"cmu_conv3x3_wgrad(64 x 64)", MODE_W3, 8, 64, 64, false, 2, 1, CMU_KNOB_WGRAD_BLOCKS,
+     [](int CA, int CB, int dt) { return cmu_dtype_size(dt) == 2 && CA % 64 == 0 && CB % 64 == 0; },
+     [](int, int) { return cmu_knob(CMU_KNOB_WGRAD_WIDE) && cmu_knob(CMU_KNOB_WGRAD_SQUARE); }, true,
+     WG_HALO_B, 3, true, MODE_W3, WG_BIAS_NONE, {nullptr, wg_launch_square<F16Traits>, wg_launch_square<BF16Traits>}},
+    // fp32 wide kernel (conv_wgrad2f.inc): Cout and Cin in whole 64-blocks -- 128 n x 64 c blocks (NAI = 4) when Cout allows, else 64 x 64
+    // with two k-parts (NAI = 2).  CMU_WGRAD_WIDE_F32=0 keeps fp32 on the first kernel (A/B switch).
+    {"cmu_conv3x3_wgrad(wide, fp32)", MODE_W3, 4, 128, 64, false, 1, 1, CMU_KNOB_WGRAD_BLOCKS,
+     [](int CA, int CB, int dt) { return dt == CMU_F32 && CA % 128 == 0 && CB % 64 == 0; }, wg_wide_f32_on, true,
+     WG_HALO_B, 3, false, MODE_W3, WG_BIAS_NONE, {wg_launch_wide_f32<4>, nullptr, nullptr}},
+    {"cmu_conv3x3_wgrad(wide, fp32)", MODE_W3, 4, 64, 64, false, 2, 1, CMU_KNOB_WGRAD_BLOCKS,
+     [](int CA, int CB, int dt) { return dt == CMU_F32 && CA % 64 == 0 && CA % 128 != 0 && CB % 64 == 0; }, wg_wide_f32_on, true,
+     WG_HALO_B, 3, false, MODE_W3, WG_BIAS_NONE, {wg_launch_wide_f32<2>, nullptr, nullptr}},
+    // the first kernel: every shape and dtype, 16 x 16 tiles and tile lists; its split count aims at CMU_WGRAD_BLOCKS1 workgroups
+    {"cmu_conv3x3_wgrad", MODE_W3, 16, 0, 0, false, 1, 1, CMU_KNOB_WGRAD_BLOCKS1,
+     [](int, int, int) { return true; }, wg_on, false,
+     WG_ANY, 0, false, MODE_W3, WG_BIAS_NONE, {wg_launch_first<F32Traits, MODE_W3>, wg_launch_first<F16Traits, MODE_W3>, wg_launch_first<BF16Traits, MODE_W3>}},
 
-extern "C" int64_t cmu_conv3x3_wgrad_ws_bytes(int B, int H, int W, int Cin, int Cout, int dt) {
+    // wide ConvTranspose kernel (conv_wgrad2.inc): 16-bit dtypes, Cout in whole 64-blocks; 256 X channels per workgroup (NXI = 4) where Cin
+    // allows -- the deeper decoder levels (CMU_WGT2_NX256=0: A/B) -- else 128 (NXI = 2)
+    {"cmu_convT2x2_wgrad(wide)", MODE_WT, 4, 64, 256, false, 1, 1, CMU_KNOB_WGRAD_BLOCKS,
+     [](int CA, int CB, int dt) { return cmu_dtype_size(dt) == 2 && CA % 64 == 0 && CB % 256 == 0; },
+     [](int, int CB) { return cmu_knob(CMU_KNOB_WGRAD_WIDE) && wg_nx256(CB); }, false,
+     WG_PLAIN, 0, false, 2, WG_BIAS_SPLITS, {nullptr, wg_launchT_wide<F16Traits, 4>, wg_launchT_wide<BF16Traits, 4>}},
+    {"cmu_convT2x2_wgrad(wide)", MODE_WT, 4, 64, 128, false, 1, 1, CMU_KNOB_WGRAD_BLOCKS,
+     [](int CA, int CB, int dt) { return cmu_dtype_size(dt) == 2 && CA % 64 == 0 && CB % 128 == 0; },
+     [](int, int CB) { return cmu_knob(CMU_KNOB_WGRAD_WIDE) && !wg_nx256(CB); }, false,
+     WG_PLAIN, 0, false, 2, WG_BIAS_SPLITS, {nullptr, wg_launchT_wide<F16Traits, 2>, wg_launchT_wide<BF16Traits, 2>}},
+    // fp32 wide ConvTranspose kernel (conv_wgrad2f.inc): 128 c x 64 n blocks.  Follows CMU_WGRAD_WIDE_F32.
+    {"cmu_convT2x2_wgrad(wide, fp32)", MODE_WT, 2, 64, 128, false, 1, 1, CMU_KNOB_WGRAD_BLOCKS,
+     [](int CA, int CB, int dt) { return dt == CMU_F32 && CA % 64 == 0 && CB % 128 == 0; }, wg_wide_f32_on, true,
+     WG_PLAIN, 3, false, 2, WG_BIAS_SUMS, {wg_launchT_wide_f32, nullptr, nullptr}},
+    {"cmu_convT2x2_wgrad", MODE_WT, 16, 0, 0, false, 1, 4, -1,
+     [](int, int, int) { return true; }, wg_on, false,
+     WG_ANY, 0, false, MODE_WT, WG_BIAS_SUMS, {wg_launch_first<F32Traits, MODE_WT>, wg_launch_first<F16Traits, MODE_WT>, wg_launch_first<BF16Traits, MODE_WT>}},
+};
+
+// Tiles, blocks, pads and the split count of form f for the dims in p; returns the bytes the form writes to the workspace
+static int64_t wg_geometry(const WGForm& f, int dt, WGParams& p) {
+    const int cw = 128 / cmu_dtype_size(dt);
+    const int a_blk = f.a_blk ? f.a_blk : cw, b_blk = f.b_blk ? f.b_blk : cw;
+    const int na = cmu_div_up(p.CA, a_blk), nb = cmu_div_up(p.CB, b_blk);
+    p.tilesX = cmu_div_up(p.W, 16);
+    p.tilesY = cmu_div_up(p.H, f.tile_h);
+    p.ntiles = p.B * p.tilesX * p.tilesY;
+    p.nAB = f.swap ? nb : na;
+    p.nBB = f.swap ? na : nb;
+    p.CApad = na * a_blk;
+    p.CBpad = nb * b_blk;
+    p.splitk = wg_splitk(na * nb, p.ntiles, f.wgs, f.aim < 0 ? 512 : cmu_knob(f.aim));
+    const int taps = f.family == MODE_W3 ? 9 : 4;
+    const int64_t bias_rows = f.bias == WG_BIAS_SUMS ? CSUM_BLOCKS : f.bias == WG_BIAS_SPLITS ? p.splitk : 0;
+    return ((int64_t)p.splitk * f.slabs * taps * p.CApad * p.CBpad + bias_rows * p.CA) * (int64_t)sizeof(float);
+}
+// both operands of one image within the range of a buffer descriptor
+static bool wg_in_range(const WGForm& f, const WGParams& p, int dt) {
+    if (f.range == WG_ANY) return true;
+    const int64_t px = (int64_t)p.H * p.W, halo = p.W + 1, es = cmu_dtype_size(dt);
+    const int64_t a_px = (f.family == MODE_WT ? 4 * px : px) + (f.range == WG_HALO_A ? halo : 0), b_px = px + (f.range == WG_HALO_B ? halo : 0);
+    return (a_px * p.lda + p.CA) * es < WG_BUF_RANGE && (b_px * p.ldb + p.CB) * es < WG_BUF_RANGE;
+}
+static bool wg_tf_aligned(const WGForm& f, const WGParams& p) {
+    return p.b_scale == nullptr || ((reinterpret_cast<uintptr_t>(p.b_scale) | reinterpret_cast<uintptr_t>(p.b_shift)) & f.tf_align) == 0;
+}
+// The form that serves the launch described by p (operands, transform, dims), its geometry filled into p.  The first row of the family whose
+// shape and knobs hold claims the shape; where its tensors are out of range or misaligned, the first kernel runs -- no later wide row.
+// tile_h: 0 for a dense launch, else the height of the tile list's tiles (16: the first kernel; 8: nullptr unless the form walks such lists).
+// (The bytes the planned form writes are wg_geometry's return value: the size queries take their maximum over the candidate rows.)
+static const WGForm* wg_plan(int family, int dt, int tile_h, WGParams& p) {
+    bool claimed = false;
+    for (const WGForm& f : WG_FORMS) {
+        if (f.family != family) continue;
+        if (f.range != WG_ANY) {
+            if (claimed || tile_h == 16 || !f.shape(p.CA, p.CB, dt) || !f.knobs(p.CA, p.CB)) continue;
+            claimed = true;
+            if (!wg_in_range(f, p, dt) || !wg_tf_aligned(f, p)) continue;
+        }
+        if (tile_h == 8 && !f.lists8) return nullptr;
+        wg_geometry(f, dt, p);
+        return &f;
+    }
+    return nullptr;
+}
+// The size queries: the largest workspace of the forms that may serve the shape, whatever the strides, the transform and (for the forms
+// marked so) the knobs turn out to be
+static int64_t wg_ws_bytes(int family, int B, int H, int W, int Cin, int Cout, int dt) {
     if (cmu_dtype_size(dt) == 0 || B <= 0 || H <= 0 || W <= 0 || Cin <= 0 || Cout <= 0) return -1;
-    WGParams p = {};
-    wg_geometry(B, H, W, Cout, Cin, dt, 1, p);
-    int64_t need = (int64_t)p.splitk * 9 * p.CApad * p.CBpad * (int64_t)sizeof(float);
-    if (wg2_shape_ok(Cout, Cin, dt) || wg2_swap_ok(Cout, Cin, dt)) {   // either kernel may run (the wide one needs 4 GiB-addressable tensors)
+    int64_t need = 0;
+    for (const WGForm& f : WG_FORMS) {
+        if (f.family != family || !f.shape(Cout, Cin, dt) || !(f.size_any_knobs || f.knobs(Cout, Cin))) continue;
         WGParams q = {};
-        wg2_geometry(B, H, W, Cout, Cin, q, !wg2_shape_ok(Cout, Cin, dt));
-        const int64_t w = (int64_t)q.splitk * 9 * q.CApad * q.CBpad * (int64_t)sizeof(float);
-        if (w > need) need = w;
-    }
-    if (cmu_dtype_size(dt) == 2 && Cout % 64 == 0 && Cin % 64 == 0) {   // the 64 x 64 form: two slabs per split
-        WGParams q = {};
-        wg2s_geometry(B, H, W, Cout, Cin, q);
-        const int64_t w = (int64_t)q.splitk * 2 * 9 * q.CApad * q.CBpad * (int64_t)sizeof(float);
-        if (w > need) need = w;
-    }
-    if (dt == CMU_F32 && Cout % 64 == 0 && Cin % 64 == 0) {   // the fp32 wide kernel (two slabs per split for 64 x 64 blocks)
-        WGParams q = {};
-        wg2f_geometry(B, H, W, Cout, Cin, q);
-        const int64_t w = (int64_t)q.splitk * (Cout % 128 == 0 ? 1 : 2) * 9 * q.CApad * q.CBpad * (int64_t)sizeof(float);
+        q.B = B; q.H = H; q.W = W; q.CA = Cout; q.CB = Cin;
+        const int64_t w = wg_geometry(f, dt, q);
         if (w > need) need = w;
     }
     return need;
 }
+
+// bias gradient of the ConvTranspose: sum of dOut over all (B,2H,2W) pixels, CSUM_BLOCKS rows of partial sums in ws_sum
+template <class TR>
+static int wg_bias_sums_t(const WGParams& p, float* ws_sum, float* dbias, hipStream_t st) {
+    const int nchunk = p.CA / TR::EPC;
+    const int cpb = nchunk < 256 ? nchunk : 256, ppb = 256 / cpb, gy = cmu_div_up(nchunk, cpb);
+    const int64_t npix = (int64_t)p.B * 4 * p.H * p.W;
+    int gx = (int)(cmu_div_up64(npix, ppb * 4) < CSUM_BLOCKS ? cmu_div_up64(npix, ppb * 4) : CSUM_BLOCKS);
+    if (gx < 1) gx = 1;
+    hipLaunchKernelGGL((channel_sum_kernel<TR>), dim3(gx, gy), dim3(256), 0, st, (const unsigned char*)p.a, p.lda, ws_sum, npix, p.CA, cpb, ppb);
+    CMU_CHECK_LAUNCH("cmu_convT2x2_wgrad(bias)");
+    hipLaunchKernelGGL(channel_sum_final_kernel, dim3(cmu_div_up(p.CA, 16)), dim3(256), 0, st, (const float*)ws_sum, gx, p.CA, dbias);
+    CMU_CHECK_LAUNCH("cmu_convT2x2_wgrad(bias final)");
+    return CMU_OK;
+}
+static int wg_bias_sums(const WGParams& p, int dt, float* ws_sum, float* dbias, hipStream_t st) { CMU_DISPATCH_DT(dt, wg_bias_sums_t, p, ws_sum, dbias, st); }
+
+// the planned form's kernel, the reduction of its slabs in slab order, and the bias gradient where the form has one
+static int wg_run(const WGForm& f, const WGParams& p, int dt, float* dW, float* dbias, hipStream_t st) {
+    const bool wt = f.family == MODE_WT;
+    if (int rc = f.launch[dt](p, st, f.name)) return rc;
+    CMU_CHECK_LAUNCH(f.name);
+    launch_wgrad_reduce((const float*)p.ws, p.splitk * f.slabs, wt ? 4 : 9, p.CApad, p.CBpad, p.CA, p.CB, dW, f.reduce_mode, st);
+    CMU_CHECK_LAUNCH(wt ? "cmu_convT2x2_wgrad(reduce)" : "cmu_conv3x3_wgrad(reduce)");
+    float* ws_sum = p.ws + (int64_t)p.splitk * f.slabs * 4 * p.CApad * p.CBpad;
+    if (f.bias == WG_BIAS_SUMS) return wg_bias_sums(p, dt, ws_sum, dbias, st);
+    if (f.bias == WG_BIAS_SPLITS) {
+        hipLaunchKernelGGL(channel_sum_final_kernel, dim3(cmu_div_up(p.CA, 16)), dim3(256), 0, st, (const float*)ws_sum, p.splitk, p.CA, dbias);
+        CMU_CHECK_LAUNCH("cmu_convT2x2_wgrad(bias final)");
+    }
+    return CMU_OK;
+}
+
+// the argument checks and the WGParams fill that the three launch entries share (a: the output gradient, b: the layer's input)
+static int wg_args(const char* name, WGParams& p, const void* x, int64_t ldx, const float* in_scale, const float* in_shift, int relu_from, const void* dA,
+                   int64_t lda, bool ptrs_ok, void* ws, int B, int H, int W, int Cin, int Cout, int dt) {
+    CMU_CHECK_ARG(ptrs_ok && ws && B > 0 && H > 0 && W > 0, "%s: null argument / bad dims", name);
+    CMU_CHECK_ARG((in_scale == nullptr) == (in_shift == nullptr), "%s: scale/shift must both be set", name);
+    CMU_CHECK_ARG(relu_from % (16 / cmu_dtype_size(dt)) == 0, "%s: relu_from=%d must be a multiple of the 16-byte chunk", name, relu_from);
+    p.a = dA; p.lda = lda; p.b = x; p.ldb = ldx; p.b_scale = in_scale; p.b_shift = in_shift; p.relu_from = relu_from;
+    p.ws = (float*)ws; p.B = B; p.H = H; p.W = W; p.CA = Cout; p.CB = Cin;
+    return CMU_OK;
+}
+
+extern "C" int64_t cmu_conv3x3_wgrad_ws_bytes(int B, int H, int W, int Cin, int Cout, int dt) { return wg_ws_bytes(MODE_W3, B, H, W, Cin, Cout, dt); }
 extern "C" int cmu_conv3x3_wgrad(const void* x, int64_t ldx, const float* in_scale, const float* in_shift, int relu_from, const void* dY,
                                  int64_t ldd, float* dW, int B, int H, int W, int Cin, int Cout, int dt, void* ws, void* stream) {
     int rc;
-    if ((rc = wg_check("cmu_conv3x3_wgrad(x)", x, ldx, Cin, dt))) return rc;
-    if ((rc = wg_check("cmu_conv3x3_wgrad(dY)", dY, ldd, Cout, dt))) return rc;
-    CMU_CHECK_ARG(dW && ws && B > 0 && H > 0 && W > 0, "cmu_conv3x3_wgrad: null argument / bad dims");
-    CMU_CHECK_ARG((in_scale == nullptr) == (in_shift == nullptr), "cmu_conv3x3_wgrad: scale/shift must both be set");
-    CMU_CHECK_ARG(relu_from % (16 / cmu_dtype_size(dt)) == 0, "cmu_conv3x3_wgrad: relu_from=%d must be a multiple of the 16-byte chunk", relu_from);
+    if ((rc = cmu_check_act("cmu_conv3x3_wgrad(x)", x, ldx, Cin, dt))) return rc;
+    if ((rc = cmu_check_act("cmu_conv3x3_wgrad(dY)", dY, ldd, Cout, dt))) return rc;
     WGParams p = {};
-    p.a = dY; p.lda = ldd; p.b = x; p.ldb = ldx; p.b_scale = in_scale; p.b_shift = in_shift; p.relu_from = relu_from;
-    p.ws = (float*)ws; p.B = B; p.H = H; p.W = W; p.CA = Cout; p.CB = Cin;
-    const int64_t px = (int64_t)H * W;   // per image: the buffer descriptors are per image
-    if (wg2_shape_ok(Cout, Cin, dt) && (px * ldd + Cout) * 2 < 0x7fff0000ll && ((px + W + 1) * ldx + Cin) * 2 < 0x7fff0000ll &&
-        (in_scale == nullptr || ((reinterpret_cast<uintptr_t>(in_scale) | reinterpret_cast<uintptr_t>(in_shift)) & 3) == 0)) {
-        wg2_geometry(B, H, W, Cout, Cin, p);
-        if (dt == CMU_F16) return wgrad3_wide_t<F16Traits, false>(p, dW, (hipStream_t)stream);
-        return wgrad3_wide_t<BF16Traits, false>(p, dW, (hipStream_t)stream);
-    }
-    // swapped roles: the halo is on dY here, the plain images are X
-    if (wg2_swap_ok(Cout, Cin, dt) && ((px + W + 1) * ldd + Cout) * 2 < 0x7fff0000ll && (px * ldx + Cin) * 2 < 0x7fff0000ll &&
-        (in_scale == nullptr || ((reinterpret_cast<uintptr_t>(in_scale) | reinterpret_cast<uintptr_t>(in_shift)) & 15) == 0)) {
-        wg2_geometry(B, H, W, Cout, Cin, p, true);
-        if (dt == CMU_F16) return wgrad3_wide_t<F16Traits, true>(p, dW, (hipStream_t)stream);
-        return wgrad3_wide_t<BF16Traits, true>(p, dW, (hipStream_t)stream);
-    }
-    if (wg2s_shape_ok(Cout, Cin, dt) && (px * ldd + Cout) * 2 < 0x7fff0000ll && ((px + W + 1) * ldx + Cin) * 2 < 0x7fff0000ll &&
-        (in_scale == nullptr || ((reinterpret_cast<uintptr_t>(in_scale) | reinterpret_cast<uintptr_t>(in_shift)) & 3) == 0)) {
-        wg2s_geometry(B, H, W, Cout, Cin, p);
-        if (dt == CMU_F16) return wgrad3_square_t<F16Traits>(p, dW, (hipStream_t)stream);
-        return wgrad3_square_t<BF16Traits>(p, dW, (hipStream_t)stream);
-    }
-    if (wg2f_shape_ok(Cout, Cin, dt) && (px * ldd + Cout) * 4 < 0x7fff0000ll && ((px + W + 1) * ldx + Cin) * 4 < 0x7fff0000ll &&
-        (in_scale == nullptr || ((reinterpret_cast<uintptr_t>(in_scale) | reinterpret_cast<uintptr_t>(in_shift)) & 3) == 0)) {
-        wg2f_geometry(B, H, W, Cout, Cin, p);
-        return Cout % 128 == 0 ? wgrad3_wide_f32_t<4>(p, dW, (hipStream_t)stream) : wgrad3_wide_f32_t<2>(p, dW, (hipStream_t)stream);
-    }
-    wg_geometry(B, H, W, Cout, Cin, dt, 1, p);
-    CMU_DISPATCH_DT(dt, wgrad3_t, p, dW, (hipStream_t)stream);
+    if ((rc = wg_args("cmu_conv3x3_wgrad", p, x, ldx, in_scale, in_shift, relu_from, dY, ldd, dW != nullptr, ws, B, H, W, Cin, Cout, dt))) return rc;
+    return wg_run(*wg_plan(MODE_W3, dt, 0, p), p, dt, dW, nullptr, (hipStream_t)stream);
 }
 
 // Sparse (SparK) weight gradient over a device-side tile list (cmu_sparse_tile_list).  The list's tile height says which kernel
-// walks it: 16 (16 x 16 pixel tiles) = the first kernel, any shape; 8 (8 x 16 tiles, the wide kernel's K tile) = the wide kernel,
-// for the shapes cmu_conv3x3_wgrad_tile_h names.  ws: cmu_conv3x3_wgrad_ws_bytes.
-static bool wg2_list_ok(int B, int H, int W, int64_t ldx, int64_t ldd, int Cin, int Cout, int dt) {
-    const int64_t px = (int64_t)H * W;
-    return wg2_shape_ok(Cout, Cin, dt) && (px * ldd + Cout) * 2 < 0x7fff0000ll && ((px + W + 1) * ldx + Cin) * 2 < 0x7fff0000ll;
-}
-static bool wg2s_list_ok(int B, int H, int W, int64_t ldx, int64_t ldd, int Cin, int Cout, int dt) {
-    const int64_t px = (int64_t)H * W;
-    return wg2s_shape_ok(Cout, Cin, dt) && (px * ldd + Cout) * 2 < 0x7fff0000ll && ((px + W + 1) * ldx + Cin) * 2 < 0x7fff0000ll;
-}
+// walks it: 16 (16 x 16 pixel tiles) = the first kernel, any shape; 8 (8 x 16 tiles, the wide kernel's K tile) = the wide kernel or the
+// 64 x 64 form, for the shapes cmu_conv3x3_wgrad_tile_h names.  ws: cmu_conv3x3_wgrad_ws_bytes.
 extern "C" int cmu_conv3x3_wgrad_tile_h(int B, int H, int W, int Cin, int Cout, int dt) {
     if (cmu_dtype_size(dt) == 0 || B <= 0 || H <= 0 || W <= 0 || Cin <= 0 || Cout <= 0) return -1;
-    return (wg2_list_ok(B, H, W, Cin, Cout, Cin, Cout, dt) || wg2s_list_ok(B, H, W, Cin, Cout, Cin, Cout, dt)) ? 8 : 16;   // (dense NHWC tensors: ld = C)
+    WGParams p = {};
+    p.B = B; p.H = H; p.W = W; p.CA = Cout; p.CB = Cin; p.lda = Cout; p.ldb = Cin;   // (dense NHWC tensors: ld = C)
+    return wg_plan(MODE_W3, dt, 0, p)->lists8 ? 8 : 16;
 }
 extern "C" int cmu_conv3x3_wgrad_tiles(const void* x, int64_t ldx, const float* in_scale, const float* in_shift, int relu_from,
                                        const void* dY, int64_t ldd, float* dW, const int* tile_list, const int* tile_count, int tile_h,
                                        int B, int H, int W, int Cin, int Cout, int dt, void* ws, void* stream) {
     int rc;
-    if ((rc = wg_check("cmu_conv3x3_wgrad_tiles(x)", x, ldx, Cin, dt))) return rc;
-    if ((rc = wg_check("cmu_conv3x3_wgrad_tiles(dY)", dY, ldd, Cout, dt))) return rc;
-    CMU_CHECK_ARG(dW && ws && tile_list && tile_count && B > 0 && H > 0 && W > 0, "cmu_conv3x3_wgrad_tiles: null argument / bad dims");
-    CMU_CHECK_ARG((in_scale == nullptr) == (in_shift == nullptr), "cmu_conv3x3_wgrad_tiles: scale/shift must both be set");
-    CMU_CHECK_ARG(relu_from % (16 / cmu_dtype_size(dt)) == 0, "cmu_conv3x3_wgrad_tiles: relu_from=%d must be a multiple of the 16-byte chunk", relu_from);
-    CMU_CHECK_ARG(tile_h == 16 || tile_h == 8, "cmu_conv3x3_wgrad_tiles: tile_h=%d (16: 16 x 16 tiles, 8: 8 x 16 tiles)", tile_h);
+    if ((rc = cmu_check_act("cmu_conv3x3_wgrad_tiles(x)", x, ldx, Cin, dt))) return rc;
+    if ((rc = cmu_check_act("cmu_conv3x3_wgrad_tiles(dY)", dY, ldd, Cout, dt))) return rc;
     WGParams p = {};
-    p.a = dY; p.lda = ldd; p.b = x; p.ldb = ldx; p.b_scale = in_scale; p.b_shift = in_shift; p.relu_from = relu_from;
-    p.ws = (float*)ws; p.B = B; p.H = H; p.W = W; p.CA = Cout; p.CB = Cin;
+    if ((rc = wg_args("cmu_conv3x3_wgrad_tiles", p, x, ldx, in_scale, in_shift, relu_from, dY, ldd, dW && tile_list && tile_count, ws, B, H, W, Cin, Cout, dt)))
+        return rc;
+    CMU_CHECK_ARG(tile_h == 16 || tile_h == 8, "cmu_conv3x3_wgrad_tiles: tile_h=%d (16: 16 x 16 tiles, 8: 8 x 16 tiles)", tile_h);
     p.tile_list = tile_list; p.tile_count = tile_count;
-    if (tile_h == 8 && wg2s_list_ok(B, H, W, ldx, ldd, Cin, Cout, dt) &&
-        (in_scale == nullptr || ((reinterpret_cast<uintptr_t>(in_scale) | reinterpret_cast<uintptr_t>(in_shift)) & 3) == 0)) {
-        wg2s_geometry(B, H, W, Cout, Cin, p);   // (the 64 x 64 form walks the same 8 x 16 lists)
-        if (dt == CMU_F16) return wgrad3_square_t<F16Traits>(p, dW, (hipStream_t)stream);
-        return wgrad3_square_t<BF16Traits>(p, dW, (hipStream_t)stream);
-    }
-    if (tile_h == 8) {
-        CMU_CHECK_ARG(wg2_list_ok(B, H, W, ldx, ldd, Cin, Cout, dt) &&
-                          (in_scale == nullptr || ((reinterpret_cast<uintptr_t>(in_scale) | reinterpret_cast<uintptr_t>(in_shift)) & 3) == 0),
-                      "cmu_conv3x3_wgrad_tiles: an 8 x 16 tile list needs a shape of the wide kernel (16-bit, Cout %% 128 == 0, Cin %% 64 == 0; "
-                      "cmu_conv3x3_wgrad_tile_h), got %d -> %d", Cin, Cout);
-        wg2_geometry(B, H, W, Cout, Cin, p);
-        if (dt == CMU_F16) return wgrad3_wide_t<F16Traits, false>(p, dW, (hipStream_t)stream);
-        return wgrad3_wide_t<BF16Traits, false>(p, dW, (hipStream_t)stream);
-    }
-    wg_geometry(B, H, W, Cout, Cin, dt, 1, p);
-    CMU_DISPATCH_DT(dt, wgrad3_t, p, dW, (hipStream_t)stream);
+    const WGForm* f = wg_plan(MODE_W3, dt, tile_h, p);
+    CMU_CHECK_ARG(f != nullptr,
+                  "cmu_conv3x3_wgrad_tiles: an 8 x 16 tile list needs a shape of the wide kernel (16-bit, Cout %% 128 == 0, Cin %% 64 == 0; "
+                  "cmu_conv3x3_wgrad_tile_h), got %d -> %d", Cin, Cout);
+    return wg_run(*f, p, dt, dW, nullptr, (hipStream_t)stream);
 }
 
-extern "C" int64_t cmu_convT2x2_wgrad_ws_bytes(int B, int H, int W, int Cin, int Cout, int dt) {
-    if (cmu_dtype_size(dt) == 0 || B <= 0 || H <= 0 || W <= 0 || Cin <= 0 || Cout <= 0) return -1;
-    WGParams p = {};
-    wg_geometry(B, H, W, Cout, Cin, dt, 4, p);
-    int64_t need = ((int64_t)p.splitk * 4 * p.CApad * p.CBpad + (int64_t)CSUM_BLOCKS * Cout) * (int64_t)sizeof(float);
-    if (wgT2_shape_ok(Cout, Cin, dt)) {
-        WGParams q = {};
-        wgT2_geometry(B, H, W, Cout, Cin, q);
-        const int64_t w = (int64_t)q.splitk * ((int64_t)4 * Cout * Cin + Cout) * (int64_t)sizeof(float);
-        if (w > need) need = w;
-    }
-    if (dt == CMU_F32 && Cout % 64 == 0 && Cin % 128 == 0) {   // the fp32 wide form
-        WGParams q = {};
-        wgT2f_geometry(B, H, W, Cout, Cin, q);
-        const int64_t w = ((int64_t)q.splitk * 4 * Cout * Cin + (int64_t)CSUM_BLOCKS * Cout) * (int64_t)sizeof(float);
-        if (w > need) need = w;
-    }
-    return need;
-}
+extern "C" int64_t cmu_convT2x2_wgrad_ws_bytes(int B, int H, int W, int Cin, int Cout, int dt) { return wg_ws_bytes(MODE_WT, B, H, W, Cin, Cout, dt); }
 extern "C" int cmu_convT2x2_wgrad(const void* x, int64_t ldx, const float* in_scale, const float* in_shift, int relu_from, const void* dOut,
                                   int64_t ldd, float* dW, float* dbias, int B, int H, int W, int Cin, int Cout, int dt, void* ws,
                                   void* stream) {
     int rc;
-    if ((rc = wg_check("cmu_convT2x2_wgrad(x)", x, ldx, Cin, dt))) return rc;
-    if ((rc = wg_check("cmu_convT2x2_wgrad(dOut)", dOut, ldd, Cout, dt))) return rc;
-    CMU_CHECK_ARG(dW && dbias && ws && B > 0 && H > 0 && W > 0, "cmu_convT2x2_wgrad: null argument / bad dims");
-    CMU_CHECK_ARG((in_scale == nullptr) == (in_shift == nullptr), "cmu_convT2x2_wgrad: scale/shift must both be set");
-    CMU_CHECK_ARG(relu_from % (16 / cmu_dtype_size(dt)) == 0, "cmu_convT2x2_wgrad: relu_from=%d must be a multiple of the 16-byte chunk", relu_from);
+    if ((rc = cmu_check_act("cmu_convT2x2_wgrad(x)", x, ldx, Cin, dt))) return rc;
+    if ((rc = cmu_check_act("cmu_convT2x2_wgrad(dOut)", dOut, ldd, Cout, dt))) return rc;
     WGParams p = {};
-    p.a = dOut; p.lda = ldd; p.b = x; p.ldb = ldx; p.b_scale = in_scale; p.b_shift = in_shift; p.relu_from = relu_from;
-    p.ws = (float*)ws; p.B = B; p.H = H; p.W = W; p.CA = Cout; p.CB = Cin;
-    const int64_t px = (int64_t)H * W;   // per image: the buffer descriptors are per image
-    if (wgT2_shape_ok(Cout, Cin, dt) && (4 * px * ldd + Cout) * 2 < 0x7fff0000ll && (px * ldx + Cin) * 2 < 0x7fff0000ll) {
-        wgT2_geometry(B, H, W, Cout, Cin, p);
-        if (dt == CMU_F16) return wgradT_wide_t<F16Traits>(p, dW, dbias, (hipStream_t)stream);
-        return wgradT_wide_t<BF16Traits>(p, dW, dbias, (hipStream_t)stream);
-    }
-    if (wgT2f_shape_ok(Cout, Cin, dt) && (4 * px * ldd + Cout) * 4 < 0x7fff0000ll && (px * ldx + Cin) * 4 < 0x7fff0000ll &&
-        (in_scale == nullptr || ((reinterpret_cast<uintptr_t>(in_scale) | reinterpret_cast<uintptr_t>(in_shift)) & 3) == 0)) {
-        wgT2f_geometry(B, H, W, Cout, Cin, p);
-        return wgradT_wide_f32(p, dW, dbias, (float*)ws + (int64_t)p.splitk * 4 * Cout * Cin, (hipStream_t)stream);
-    }
-    wg_geometry(B, H, W, Cout, Cin, dt, 4, p);
-    float* ws_sum = (float*)ws + (int64_t)p.splitk * 4 * p.CApad * p.CBpad;
-    const int dtc = dt;
-    switch (dtc) {
-        case CMU_F32: return wgradT_t<F32Traits>(p, dW, dbias, ws_sum, (hipStream_t)stream);
-        case CMU_F16: return wgradT_t<F16Traits>(p, dW, dbias, ws_sum, (hipStream_t)stream);
-        case CMU_BF16: return wgradT_t<BF16Traits>(p, dW, dbias, ws_sum, (hipStream_t)stream);
-    }
-    cmu_set_error("cmu_convT2x2_wgrad: unknown dtype %d", dt);
-    return CMU_ERR_ARG;
+    if ((rc = wg_args("cmu_convT2x2_wgrad", p, x, ldx, in_scale, in_shift, relu_from, dOut, ldd, dW && dbias, ws, B, H, W, Cin, Cout, dt))) return rc;
+    return wg_run(*wg_plan(MODE_WT, dt, 0, p), p, dt, dW, dbias, (hipStream_t)stream);
 }

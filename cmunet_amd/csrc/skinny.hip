@@ -136,19 +136,11 @@ extern "C" int cmu_skinny_gemm_fwd(const float* x, const float* w, const float* 
     CMU_CHECK_ARG(cmu_aligned16(x) && cmu_aligned16(w), "cmu_skinny_gemm_fwd: x / w must be 16-byte aligned");
     int64_t kc;
     const int splits = skf_splits(N, K, &kc);
-    static CmuPerDevice attr_set;   // hipFuncSetAttribute is per device
-    if (!attr_set.done()) {
-        hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void*>(&skinny_fwd_kernel), hipFuncAttributeMaxDynamicSharedMemorySize, SKF_LDS_BYTES);
-        if (e != hipSuccess) {
-            cmu_set_error("cmu_skinny_gemm_fwd: hipFuncSetAttribute(%d B LDS): %s", SKF_LDS_BYTES, hipGetErrorString(e));
-            return CMU_ERR_LAUNCH;
-        }
-        attr_set.mark();
-    }
     for (int m0 = 0; m0 < M; m0 += 32) {      // row groups of 32: the slab is reused (same stream: the group's reduce precedes the next kernel)
         const int Mg = M - m0 < 32 ? M - m0 : 32;
-        hipLaunchKernelGGL(skinny_fwd_kernel, dim3(cmu_div_up(N, 128), splits), dim3(256), SKF_LDS_BYTES, (hipStream_t)stream, x + (int64_t)m0 * K, w,
-                           (float*)ws, Mg, N, K, kc);
+        if (int rc = cmu_launch_lds<&skinny_fwd_kernel>(dim3(cmu_div_up(N, 128), splits), dim3(256), SKF_LDS_BYTES, (hipStream_t)stream, "cmu_skinny_gemm_fwd",
+                                                        x + (int64_t)m0 * K, w, (float*)ws, Mg, N, K, kc))
+            return rc;
         CMU_CHECK_LAUNCH("cmu_skinny_gemm_fwd");
         hipLaunchKernelGGL(skinny_fwd_reduce_kernel, dim3((unsigned)cmu_div_up64((int64_t)Mg * N, 256)), dim3(256), 0, (hipStream_t)stream,
                            (const float*)ws, bias, y + (int64_t)m0 * N, Mg, N, splits);

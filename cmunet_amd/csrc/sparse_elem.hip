@@ -182,14 +182,6 @@ __global__ __launch_bounds__(256) void bn_bwd_apply_cells_kernel(const unsigned 
     }
 }
 
-static int check_cells_act(const char* name, const void* a, int64_t lda, int C, int dt) {
-    const int es = cmu_dtype_size(dt);
-    CMU_CHECK_ARG(es > 0, "%s: bad dtype %d", name, dt);
-    const int epc = 16 / es;
-    CMU_CHECK_ARG(a && cmu_aligned16(a) && C > 0 && C % epc == 0 && lda % epc == 0 && lda >= C, "%s: null / unaligned tensor or C=%d, ld=%lld not multiples of %d",
-                  name, C, (long long)lda, epc);
-    return CMU_OK;
-}
 #define CMU_CELLS_GEOMETRY(name, pooled, maxlog)                                                                                             \
     CellGeo g;                                                                                                                               \
     if (!cells_geometry(B, H, W, C, 16 / cmu_dtype_size(dt), f, maxlog, pooled, &g)) {                                                       \
@@ -215,9 +207,9 @@ extern "C" int cmu_bn_bwd_apply_cells(const void* dA, int64_t ldd, const void* y
                                       const float* save_mean, const float* save_invstd, const float* coef, void* dY, int64_t ldo,
                                       const uint8_t* active, int f, int ring, int B, int H, int W, int C, int dt, void* stream) {
     int rc;
-    if ((rc = check_cells_act("cmu_bn_bwd_apply_cells(dA)", dA, ldd, C, dt))) return rc;
-    if ((rc = check_cells_act("cmu_bn_bwd_apply_cells(y)", y, ldy, C, dt))) return rc;
-    if ((rc = check_cells_act("cmu_bn_bwd_apply_cells(dY)", dY, ldo, C, dt))) return rc;
+    if ((rc = cmu_check_act("cmu_bn_bwd_apply_cells(dA)", dA, ldd, C, dt))) return rc;
+    if ((rc = cmu_check_act("cmu_bn_bwd_apply_cells(y)", y, ldy, C, dt))) return rc;
+    if ((rc = cmu_check_act("cmu_bn_bwd_apply_cells(dY)", dY, ldo, C, dt))) return rc;
     CMU_CHECK_ARG(scale && shift && save_mean && save_invstd && coef && active, "cmu_bn_bwd_apply_cells: null argument");
     CMU_CELLS_GEOMETRY("cmu_bn_bwd_apply_cells", false, 10)
     CMU_DISPATCH_DT(dt, bn_bwd_apply_cells_t, dA, ldd, y, ldy, scale, shift, save_mean, save_invstd, coef, dY, ldo, active, g, C, ring,
@@ -333,8 +325,8 @@ static int mask_select_cells_t(const void* x, int64_t ldx, const float* scale, c
 extern "C" int cmu_mask_select_cells(const void* x, int64_t ldx, const float* scale, const float* shift, int relu, const uint8_t* active, int f,
                                      int ring, const float* fill, void* out, int64_t ldo, int B, int H, int W, int C, int dt, void* stream) {
     int rc;
-    if ((rc = check_cells_act("cmu_mask_select_cells(x)", x, ldx, C, dt))) return rc;
-    if ((rc = check_cells_act("cmu_mask_select_cells(out)", out, ldo, C, dt))) return rc;
+    if ((rc = cmu_check_act("cmu_mask_select_cells(x)", x, ldx, C, dt))) return rc;
+    if ((rc = cmu_check_act("cmu_mask_select_cells(out)", out, ldo, C, dt))) return rc;
     CMU_CHECK_ARG(active && (scale == nullptr) == (shift == nullptr), "cmu_mask_select_cells: null patch map, or only one of scale / shift");
     CMU_CELLS_GEOMETRY("cmu_mask_select_cells", false, 10)
     CMU_CHECK_ARG(!(ring && fill), "cmu_mask_select_cells: border-frame zeroing and a fill vector exclude each other");
@@ -439,10 +431,10 @@ extern "C" int cmu_maxpool_bwd_cells(const void* dP, int64_t ldp, const void* dS
                                      const float* shift, const uint8_t* active, int f, void* dA, int64_t lda, int B, int H, int W, int C, int dt,
                                      void* stream) {
     int rc;
-    if ((rc = check_cells_act("cmu_maxpool_bwd_cells(dP)", dP, ldp, C, dt))) return rc;
-    if ((rc = check_cells_act("cmu_maxpool_bwd_cells(y)", y, ldy, C, dt))) return rc;
-    if ((rc = check_cells_act("cmu_maxpool_bwd_cells(dA)", dA, lda, C, dt))) return rc;
-    if (dSkip && (rc = check_cells_act("cmu_maxpool_bwd_cells(dSkip)", dSkip, lds, C, dt))) return rc;
+    if ((rc = cmu_check_act("cmu_maxpool_bwd_cells(dP)", dP, ldp, C, dt))) return rc;
+    if ((rc = cmu_check_act("cmu_maxpool_bwd_cells(y)", y, ldy, C, dt))) return rc;
+    if ((rc = cmu_check_act("cmu_maxpool_bwd_cells(dA)", dA, lda, C, dt))) return rc;
+    if (dSkip && (rc = cmu_check_act("cmu_maxpool_bwd_cells(dSkip)", dSkip, lds, C, dt))) return rc;
     CMU_CHECK_ARG(active && scale && shift && H % 2 == 0 && W % 2 == 0, "cmu_maxpool_bwd_cells: null argument / odd level");
     CMU_CELLS_GEOMETRY("cmu_maxpool_bwd_cells", true, 9)
     CMU_DISPATCH_DT(dt, maxpool_bwd_cells_t, dP, ldp, dSkip, lds, y, ldy, scale, shift, dA, lda, active, g, (hipStream_t)stream);
@@ -616,7 +608,7 @@ extern "C" int64_t cmu_cells_channel_sum_ws_bytes(int C) { return (int64_t)CSUM_
 extern "C" int cmu_cells_channel_sum(const void* x, int64_t ldx, const uint8_t* active, int f, int invert, float* out, void* ws, int B, int H, int W,
                                      int C, int dt, void* stream) {
     int rc;
-    if ((rc = check_cells_act("cmu_cells_channel_sum(x)", x, ldx, C, dt))) return rc;
+    if ((rc = cmu_check_act("cmu_cells_channel_sum(x)", x, ldx, C, dt))) return rc;
     CMU_CHECK_ARG(active && out && ws, "cmu_cells_channel_sum: null argument");
     CMU_CELLS_GEOMETRY("cmu_cells_channel_sum", false, 10)
     CMU_DISPATCH_DT(dt, cells_channel_sum_t, x, ldx, active, invert, g, C, out, (float*)ws, (hipStream_t)stream);
@@ -632,7 +624,7 @@ extern "C" int cmu_cells_stats_rows(void) { return CSUM_ROWS; }
 extern "C" int cmu_cells_channel_stats(const void* x, int64_t ldx, const uint8_t* active, int f, float* slab, int B, int H, int W, int C, int dt,
                                        void* stream) {
     int rc;
-    if ((rc = check_cells_act("cmu_cells_channel_stats(x)", x, ldx, C, dt))) return rc;
+    if ((rc = cmu_check_act("cmu_cells_channel_stats(x)", x, ldx, C, dt))) return rc;
     CMU_CHECK_ARG(active && slab, "cmu_cells_channel_stats: null argument");
     CMU_CELLS_GEOMETRY("cmu_cells_channel_stats", false, 10)
     CMU_DISPATCH_DT(dt, cells_channel_stats_t, x, ldx, active, g, C, slab, (hipStream_t)stream);
@@ -649,8 +641,8 @@ extern "C" int cmu_bn_bwd_reduce_cells(const void* dA, int64_t ldd, const void* 
                                        const float* save_mean, const float* save_invstd, float* dgamma, float* dbeta, float* coef,
                                        const uint8_t* active, int f, int64_t count, int B, int H, int W, int C, int dt, void* ws, void* stream) {
     int rc;
-    if ((rc = check_cells_act("cmu_bn_bwd_reduce_cells(dA)", dA, ldd, C, dt))) return rc;
-    if ((rc = check_cells_act("cmu_bn_bwd_reduce_cells(y)", y, ldy, C, dt))) return rc;
+    if ((rc = cmu_check_act("cmu_bn_bwd_reduce_cells(dA)", dA, ldd, C, dt))) return rc;
+    if ((rc = cmu_check_act("cmu_bn_bwd_reduce_cells(y)", y, ldy, C, dt))) return rc;
     CMU_CHECK_ARG(scale && shift && save_mean && save_invstd && coef && ws && active && count > 0, "cmu_bn_bwd_reduce_cells: null argument");
     CMU_CELLS_GEOMETRY("cmu_bn_bwd_reduce_cells", false, 10)
     {

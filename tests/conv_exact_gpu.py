@@ -257,7 +257,7 @@ def gather_rule(case, dt, cus, capacity, base=None):
 def wgrad3_tiles_rule(case, dt, base=None):
     """cmu_conv3x3_wgrad_tiles: the list's tile height names the kernel -- 16: the first kernel, any shape; 8: the 64 x 64 form where it
     serves the shape, else the wide kernel (never swapped) -> (kernel tag, form, splits, dense tile count).  The splits are the dense
-    launch's (wg_geometry / wg2_geometry / wg2s_geometry), whatever the list's count."""
+    launch's (wg_geometry on the form's row of WG_FORMS), whatever the list's count."""
     B, H, W, CB, CA = case["shape"]
     kn = knob_values(case, base)
     assert kn["WGRAD_BLOCKS"] >= 8 and kn["WGRAD_BLOCKS1"] >= 8, "a value below the table's floor (8) falls back to the default"
@@ -336,6 +336,15 @@ def wgradT_ws_bytes(case, dt, base=None):
         s = split_class(kn["WGRAD_BLOCKS"] // ((CA // 64) * (CB // 128)), B * cdiv(W, 16) * cdiv(H, 2))[0]
         need = max(need, (s * 4 * CA * CB + 256 * CA) * 4)
     return need
+
+
+def wgrad3_tile_h(case, dt, base=None):
+    """cmu_conv3x3_wgrad_tile_h restated: 8 where the dense launch on contiguous tensors runs the wide kernel unswapped or the 64 x 64
+    form -- the rule names one of them and an image of dY, and of X with its halo row, lies within a buffer descriptor's range -- else 16."""
+    B, H, W, CB, CA = case["shape"]
+    kernel, form = wgrad3_rule(case, dt, base)[:2]
+    in_range = (H * W * CA + CA) * ES[dt] < 0x7fff0000 and ((H * W + W + 1) * CB + CB) * ES[dt] < 0x7fff0000
+    return 8 if in_range and kernel in ("conv_wgrad2_kernel", "conv_wgrad2s_kernel") and not form.get("SWAP") else 16
 
 
 def slab_bytes(case, dt, kernel, splits):

@@ -2,7 +2,7 @@
 conv_wgrad2f_kernel, conv_wgradT2_kernel with 128 and 256 X channels per workgroup, conv_wgradT2f_kernel) and their split-K reductions
 pinned bit for bit: ``cmu_conv3x3_wgrad`` and ``cmu_convT2x2_wgrad`` (with ``dbias``) against the exact float64 references of
 conv_exact_ref.py, on integer operands and on impulses in dY (dW is then the window of x around each pixel: one dropped pixel cannot hide).
-The split-K geometry of wg_geometry / wg2_geometry / wgT2_geometry is restated in conv_exact_gpu.py and tied to the library
+The split-K geometry of every form (the rows of WG_FORMS, through wg_plan and wg_geometry) is restated in conv_exact_gpu.py and tied to the library
 through the workspace size it reports (cmu_*_wgrad_ws_bytes is a function of the same split counts); CMU_WGRAD_BLOCKS / CMU_WGRAD_BLOCKS1
 steer it to one split, equal splits, a short last split and more splits than tiles, and every case asserts the one it is named after.
 ``torch.equal`` on the bits is the only comparison."""
