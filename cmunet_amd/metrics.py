@@ -37,6 +37,8 @@ Losses for thin, rare foregrounds (no reference counterpart; DESIGN.md section 4
 ``cmu_focal_fwd`` / ``_bwd`` (label maps or one-hot planes), ``TverskyLoss`` from the pair's counter table (``tversky_from_counters``),
 ``BoundaryLoss`` and ``HausdorffDTLoss`` on ``cmu_softmax_map_fwd`` / ``_bwd`` with distance maps from the exact on-device transform
 (``signed_distance_maps``, ``distance_fields``: ``cmu_edt_columns`` / ``cmu_edt_rows`` / ``cmu_distance_field``).
+``LovaszSoftmaxLoss``, the surrogate of the Jaccard index itself: ``cmu_lovasz_keys`` -> ``cmu_sort_u64`` (a
+hand-written segmented key sort) -> ``cmu_lovasz_grad``; its backward is ``cmu_softmax_map_bwd``.
 """
 import collections
 import math
@@ -1379,6 +1381,81 @@ class HausdorffDTLoss(Loss):
         fields = self._fields(lg.detach().contiguous(), _label_map("HausdorffDTLoss", y, K)[0], keep)
         table = _SoftmaxMapFn.apply(lg, fields, y, keep, "squared")
         return table.sum() / float(B * len(keep) * H * W)
+
+
+# ---------------------------------------------------------------------------------------------
+# The Lovasz-Softmax loss (no reference counterpart; csrc/lovasz.hip on the segmented key sort of csrc/key_sort.hip, DESIGN.md
+# section 4.26)
+# ---------------------------------------------------------------------------------------------
+class _LovaszFn(torch.autograd.Function):
+    """The loss as a 0-dim fp64 tensor.  Forward: keys -> sort -> Jaccard gradient, which leaves d loss / d p as a weight map; the
+    backward is one call of the map-weighted softmax backward with the incoming gradient in each of its K slots."""
+
+    @staticmethod
+    def forward(ctx, x, target, onehot, keep, per_image, classes_all, ignore_index):
+        xc = x.detach().contiguous()
+        B, K, H, W = xc.shape
+        sz = ops.lovasz_sizes(B, K, H, W, keep, per_image)
+        keys = torch.empty((sz["rows"], sz["n"]), dtype=torch.int64, device=xc.device)
+        counts = torch.empty(sz["counts"], dtype=torch.int64, device=xc.device)
+        ops.lovasz_keys(xc, target, onehot, keep, per_image, ignore_index, keys, counts)
+        ranked = ops.sort_u64(keys, scratch=keys)                 # (the unsorted keys are not needed again: they are the scratch)
+        wmap = torch.empty_like(xc)
+        out = torch.empty(sz["out"], dtype=torch.float64, device=xc.device)
+        ops.lovasz_grad(ranked, counts, keep, per_image, classes_all, wmap, out)
+        ctx.save_for_backward(xc, wmap)
+        ctx.keep = keep
+        return out[0].clone()
+
+    @staticmethod
+    def backward(ctx, g):
+        xc, wmap = ctx.saved_tensors
+        dx = torch.empty_like(xc)
+        ops.softmax_map_bwd(xc, wmap, None, ctx.keep, "linear", g.reshape(1).expand(xc.shape[1]).contiguous(), dx)
+        return dx, None, None, None, None, None, None
+
+
+class LovaszSoftmaxLoss(Loss):
+    """Lovasz-Softmax (Berman et al., 2018), the convex surrogate of the Jaccard index, on logits (B,K,H,W), 2 <= K <= 8, against a
+    label map ((B,H,W) or (B,1,H,W) of int64 / int32 / uint8 / fp32 / fp64, as ``FocalLoss`` takes it) or one-hot planes of the
+    logits' shape (fp32 / fp64; the arg-max over the channels is the label, and nothing is ignored).  Per class c the errors
+    1 - p_c on the class's pixels and p_c elsewhere are sorted in descending order (equal ones by pixel index) and weighted by the
+    Jaccard index's gradient along that order.  ``classes``: 'present' averages over the classes that occur in the segment, 'all' over
+    all classes, a list of class ids over that list.  ``per_image``: a segment is one image and the images' losses are averaged;
+    else the whole batch is one segment.  Pixels labelled ``ignore_index`` take no part.  No class present, or every pixel
+    ignored: 0 with a zero gradient.  A label outside [0, K) that is not ``ignore_index`` makes the value NaN and the gradient zero."""
+
+    def __init__(self, classes="present", per_image=False, ignore_index=-100, activation="softmax", **kwargs):
+        super().__init__(**kwargs)
+        _check_map_loss("LovaszSoftmaxLoss", activation, None)
+        if isinstance(classes, str):
+            if classes not in ("present", "all"):
+                raise ValueError(f"LovaszSoftmaxLoss: classes is 'present', 'all' or a list of class ids, got {classes!r}")
+        else:
+            classes = sorted(set(int(c) for c in classes))
+            if not classes or classes[0] < 0 or classes[-1] >= ops.SEG_MAX_K:
+                raise ValueError(f"LovaszSoftmaxLoss: class ids in 0..{ops.SEG_MAX_K - 1}, got {classes}")
+        self.classes, self.per_image, self.ignore_index, self.activation = classes, bool(per_image), int(ignore_index), activation
+
+    def forward(self, y_pr, y_gt):
+        _check_device("LovaszSoftmaxLoss", y_pr, y_gt)
+        _check_index_input("LovaszSoftmaxLoss", y_pr)
+        B, K, H, W = y_pr.shape
+        onehot = y_gt.shape == y_pr.shape
+        if not onehot:
+            if y_gt.dim() == 4 and y_gt.shape[1] == 1:
+                y_gt = y_gt[:, 0]
+            if y_gt.shape != (B, H, W):
+                raise NotImplementedError(f"LovaszSoftmaxLoss: a label map (B,1,H,W) / (B,H,W) or one-hot planes for input {tuple(y_pr.shape)}, got {tuple(y_gt.shape)}")
+        keep = list(range(K)) if isinstance(self.classes, str) else self.classes
+        if keep[-1] >= K:
+            raise ValueError(f"LovaszSoftmaxLoss: class {keep[-1]} of {K} classes")
+        y = y_gt.detach()
+        if onehot:
+            y = (y if y.dtype in ops.ICE_ONEHOT_KINDS else y.float()).contiguous()
+        else:
+            y = (y if y.dtype in ops.ICE_LABEL_KINDS else y.long()).contiguous()
+        return _LovaszFn.apply(y_pr.float(), y, onehot, keep, self.per_image, self.classes != "present", self.ignore_index)
 
 
 # ---------------------------------------------------------------------------------------------

@@ -1730,3 +1730,87 @@ def distance_field(d2_to, d2_from, field, plane, mode="signed", alpha=2.0, d2_to
     call("cmu_distance_field", _p(d2_to), _p(d2_from), _p(d2_to_b), _p(d2_from_b), FIELD_MODES[mode], float(alpha), _p(field), int(plane),
          B, K, H, W, _stream())
     return field
+
+
+# ---- segmented key sort and the Lovasz-Softmax loss (csrc/key_sort.hip, csrc/lovasz.hip) -----
+def sort_tile_keys():
+    """Keys per tile of ``sort_u64`` (cmu_sort_tile_keys): segments of up to that many keys need no scratch."""
+    return int(_lib.lib().cmu_sort_tile_keys())
+
+
+def _keys_check(what, name, t, shape, device):
+    if t.dtype != torch.int64 or tuple(t.shape) != tuple(shape) or not t.is_contiguous() or t.device != device:
+        raise ValueError(f"{what}: {name} must be a contiguous int64 tensor of shape {tuple(shape)} on the keys' device")
+    return t
+
+
+def sort_u64(keys, out=None, scratch=None):
+    """keys (S,n) int64 holding uint64 bit patterns -> ``out`` (S,n): every row sorted ascending AS UNSIGNED 64-bit integers
+    (cmu_sort_u64).  ``scratch`` (S,n) is needed when n > ``sort_tile_keys()`` and allocated when not given; it may be ``keys``
+    itself, which is then overwritten -- otherwise ``keys`` is left as it was."""
+    if not keys.is_cuda:
+        raise RuntimeError("sort_u64 runs on the GPU only; there is no CPU fallback in this package")
+    if keys.dtype != torch.int64 or keys.dim() != 2 or keys.numel() == 0 or not keys.is_contiguous():
+        raise ValueError(f"sort_u64: a non-empty contiguous (S,n) int64 tensor, got {tuple(keys.shape)} {keys.dtype}")
+    S, n = keys.shape
+    out = torch.empty_like(keys) if out is None else _keys_check("sort_u64", "out", out, keys.shape, keys.device)
+    if n > sort_tile_keys():
+        scratch = torch.empty_like(keys) if scratch is None else _keys_check("sort_u64", "scratch", scratch, keys.shape, keys.device)
+        if scratch.data_ptr() == out.data_ptr():
+            raise ValueError("sort_u64: out and scratch are two buffers")
+    else:
+        scratch = None
+    if out.data_ptr() == keys.data_ptr():
+        raise ValueError("sort_u64: out is a buffer of its own")
+    call("cmu_sort_u64", _p(keys), _p(out), _p(scratch), S, n, _stream())
+    return out
+
+
+def lovasz_sizes(B, K, H, W, keep=None, per_image=False):
+    """The tensor sizes of ``lovasz_keys`` / ``lovasz_grad`` in closed form: S segments of n pixels, ``rows`` = S x kept classes sorted
+    rows of n keys, ``tiles`` = ceil(n / sort_tile_keys()) per row; counts holds S (K + 1) + 1 int64, out 1 + 2 S + S K fp64,
+    tile_fg and partials rows x tiles each."""
+    keep = list(range(K)) if keep is None else list(keep)
+    S, n = (B, H * W) if per_image else (1, B * H * W)
+    rows, tiles = S * len(keep), -(-n // sort_tile_keys())
+    return {"S": S, "n": n, "rows": rows, "tiles": tiles, "counts": S * (K + 1) + 1, "out": 1 + 2 * S + S * K, "scratch": rows * tiles}
+
+
+def _lovasz_args(x, keep, per_image):
+    B, K, H, W = x.shape
+    assert 2 <= K <= SEG_MAX_K and B <= 65535
+    keep = list(range(K)) if keep is None else list(keep)
+    assert keep and keep == sorted(set(keep)) and 0 <= keep[0] and keep[-1] < K
+    sz = lovasz_sizes(B, K, H, W, keep, per_image)
+    assert sz["n"] < 2 ** 31, "a segment holds fewer than 2^31 pixels"
+    return B, K, H, W, keep_mask(keep), sz
+
+
+def lovasz_keys(x, target, onehot, keep, per_image, ignore_index, keys, counts):
+    """keys (rows,n) int64 = the sort keys of the Lovasz errors of (B,K,H,W) fp32 logits against a (B,H,W) label plane, or (``onehot``)
+    K planes whose arg-max is the label; counts (S (K + 1) + 1 int64) = valid and per-class pixels of every segment, then the labels
+    out of range (cmu_lovasz_keys; sizes: ``lovasz_sizes``)."""
+    B, K, H, W, mask, sz = _lovasz_args(x, keep, per_image)
+    kind = _ice_args(x, target, onehot, None, None)[4]
+    assert keys.dtype == torch.int64 and keys.numel() == sz["rows"] * sz["n"] and keys.is_contiguous() and keys.is_cuda
+    assert counts.dtype == torch.int64 and counts.numel() == sz["counts"] and counts.is_contiguous() and counts.is_cuda
+    call("cmu_lovasz_keys", _p(_f32c(x)), _p(target), kind, mask, int(bool(per_image)), int(ignore_index), _p(keys), _p(counts), B, K, H, W,
+         _stream())
+
+
+def lovasz_grad(sorted_keys, counts, keep, per_image, classes_all, wmap, out, tile_fg=None, partials=None):
+    """From the sorted rows of ``lovasz_keys``: wmap (B,K,H,W) fp32 = d loss / d p (-+ coef g at each pixel's rank), out (1 + 2 S + S K
+    fp64) = [loss | L_s | coef_s | per-class losses]; ``classes_all``: every kept class counts, else those present in the segment
+    (cmu_lovasz_grad).  tile_fg (int64) / partials (fp64): rows x tiles scratch each, allocated when not given."""
+    B, K, H, W, mask, sz = _lovasz_args(wmap, keep, per_image)
+    assert sorted_keys.dtype == torch.int64 and sorted_keys.numel() == sz["rows"] * sz["n"] and sorted_keys.is_contiguous() and sorted_keys.is_cuda
+    assert counts.dtype == torch.int64 and counts.numel() == sz["counts"] and counts.is_contiguous()
+    assert out.dtype == torch.float64 and out.numel() == sz["out"] and out.is_contiguous()
+    if tile_fg is None:
+        tile_fg = torch.empty(sz["scratch"], dtype=torch.int64, device=wmap.device)
+    if partials is None:
+        partials = torch.empty(sz["scratch"], dtype=torch.float64, device=wmap.device)
+    assert tile_fg.dtype == torch.int64 and tile_fg.numel() >= sz["scratch"] and tile_fg.is_contiguous()
+    assert partials.dtype == torch.float64 and partials.numel() >= sz["scratch"] and partials.is_contiguous()
+    call("cmu_lovasz_grad", _p(sorted_keys), _p(counts), mask, int(bool(per_image)), int(bool(classes_all)), _p(_f32c(wmap)), _p(tile_fg),
+         _p(partials), _p(out), B, K, H, W, _stream())

@@ -1092,6 +1092,49 @@ int cmu_softmax_map_bwd(const float* logits, const float* wmap, const void* y, i
 int cmu_distance_field(const int32_t* d2_to, const int32_t* d2_from, const int32_t* d2_to_b, const int32_t* d2_from_b, int mode,
                        double alpha, float* field, int plane, int B, int K, int H, int W, void* stream);
 
+/* ---------------------------------------------------------------------------------------------
+ * A segmented key sort and the Lovasz-Softmax loss built on it (csrc/key_sort.hip, csrc/key_sort.h, csrc/lovasz.hip, DESIGN.md
+ * section 4.26; no reference counterpart).  No floating-point atomics, no host sync, the same bits on every call.  There is no
+ * workspace query: scratch is the explicit tensors named below, sized in closed form; none needs initialisation, and every element of
+ * every output is written on every call.
+ *
+ * cmu_sort_u64: S segments of n keys each, at keys + s n, every segment sorted ascending on its own into out + s n.  scratch: S n
+ * keys, needed when n > T = cmu_sort_tile_keys() (else it may be NULL); it may be `keys` itself, whose contents are then lost --
+ * otherwise keys is left as it was.  out is neither of them.  One launch sorts tiles of T keys in LDS (a bitonic network), then
+ * ceil(log2(ceil(n / T))) launches merge runs pairwise, partitioned by merge path; a tile never crosses a segment.  The launch count
+ * depends on (S, n) alone.  S ceil(n / T) < 2^31.                                                                                      */
+int cmu_sort_tile_keys(void);
+int cmu_sort_u64(const uint64_t* keys, uint64_t* out, uint64_t* scratch, int64_t S, int64_t n, void* stream);
+/* The Lovasz-Softmax loss (Berman et al., 2018) of logits x (B,K,H,W) fp32, 2 <= K <= 8, B <= 65535, over the classes of keep_mask
+ * (bit c = class c; Kk of them).  A segment is the whole batch (per_image = 0: S = 1, n = B H W) or one image (S = B, n = H W);
+ * n < 2^31.  Per kept class c and segment: e_i = 1 - p_c(i) where the label is c (foreground), else p_c(i); p is the fp32 softmax of
+ * cmu_seg_stats_fwd / cmu_index_ce_fwd (the same bits) and 1 - p one fp32 subtraction.  The errors are taken in descending order,
+ * equal ones by ascending pixel index (b, h, w) within the segment; with G the foreground count and F_r that among the first r,
+ * J_r = 1 - (G - F_r) / (G + r - F_r), g_1 = J_1, g_r = J_r - J_(r-1) (integers, one fp64 quotient, formed without the difference's
+ * cancellation), and the class's loss is sum_r e_(r) g_r in fp64.
+ *
+ * cmu_lovasz_keys: target_kind is a CMU_ICE_* code, the target as cmu_focal_fwd takes it (the arg-max of one-hot planes runs over all
+ * K channels; one-hot targets have no ignore_index).  keys: S Kk n uint64, row (s, i-th kept class) at keys + (s Kk + i) n.  A key,
+ * from the top: bit 63 "not valid" (the label is ignore_index or outside [0, K): such pixels sort behind every valid one), bits 62..32
+ * the low 31 bits of the fp32 error inverted, bits 31..1 the pixel's index in its segment, bit 0 the foreground bit (0 in a key that
+ * is not valid) -- below the index, so that it cannot influence the order.  counts: S (K + 1) + 1 int64 -- [s][0] valid pixels,
+ * [s][1 + c] pixels of label c for every c < K, then the number of labels outside [0, K) that are not ignore_index (integer atomics
+ * on a table the entry clears first: exact in any order).  Such a label is never used as an index.
+ * cmu_lovasz_grad: sorted_keys = the rows of cmu_lovasz_keys after cmu_sort_u64(S Kk segments of n).  classes_all = 0: the classes
+ * with G > 0 in the segment count ('present'); 1: all kept classes (a class with G = 0 has g = (1, 0, ..): its largest error).
+ * coef_s = 1 / (S x the classes that count in s), 0 if none does.  With Tn = ceil(n / cmu_sort_tile_keys()):
+ *   wmap     (B,K,H,W) fp32   d loss / d p_c(i) = -+ coef_s g_rank(i) (- on foreground), 0 at pixels that are not valid, at classes
+ *                             that are not kept or do not count: the weight map of cmu_softmax_map_bwd(kind 0) with g = the incoming
+ *                             gradient in each of its K slots;
+ *   out      1 + 2 S + S K fp64   [0] the loss sum_s coef_s L_s; [1 + s] L_s, the sum of the losses of the classes that count in s;
+ *                             [1 + S + s] coef_s; [1 + 2 S + s K + c] the loss of class c in s (0 if it does not count);
+ *   tile_fg  S Kk Tn int64, partials  S Kk Tn fp64   scratch: foreground keys and sum e g per tile of a sorted row.
+ * A label outside [0, K) anywhere makes out[0] NaN and the whole of wmap zero.  Sums: per-lane fp64 -> block partials -> fixed order. */
+int cmu_lovasz_keys(const float* x, const void* target, int target_kind, int keep_mask, int per_image, int64_t ignore_index,
+                    uint64_t* keys, int64_t* counts, int B, int K, int H, int W, void* stream);
+int cmu_lovasz_grad(const uint64_t* sorted_keys, const int64_t* counts, int keep_mask, int per_image, int classes_all, float* wmap,
+                    int64_t* tile_fg, double* partials, double* out, int B, int K, int H, int W, void* stream);
+
 /* Measurement support (bench.py's roofline block; no reference counterpart): the 16-bit MFMA rate this chip SUSTAINS.
  * Every wave of a one-workgroup-per-CU grid issues iters x 8 back-to-back 32x32x16 MFMAs from registers (no LDS, no
  * memory) or -- lds_fed = 1 -- the same MFMAs fed from LDS at the persistent conv kernel's ratio (6 fragment reads of 1 KB
